@@ -9,6 +9,7 @@ ranks -- no data-path collective; weak scaling.  Prints ONE JSON line on rank 0.
 
     python bench.py --gpus 1 --steps 5 --warmup 2
     python bench.py --gpus N ...            (plain invocation: spawns the N ranks itself, before anything touches a GPU)
+    python bench.py ... --dump-outputs DIR  (also writes the last timed step's outputs as DIR/<name>.npy: same arguments, same inputs)
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
         --master-port P bench.py --gpus N --steps K --warmup W
 
@@ -88,6 +89,8 @@ def parse():
     ap.add_argument("--gp-train-xl", action="store_true",
                     help="add the M = 70 001 legs to the gp_train block (d = 250, 16 667 + 3 333 collocation points, 39 GB per matrix: past 2^31 "
                          "elements; both surrogates, one fit each, about two minutes)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step returned (uz; u_hat with a surrogate) as DIR/<name>.npy, float32")
     ap.add_argument("--rehearse-on-one-gpu", action="store_true",
                     help="development only: all ranks share cuda:0 and rendezvous over gloo (a 1-GPU box cannot host RCCL ranks)")
     return ap.parse_args()
@@ -242,6 +245,25 @@ def measure(ranks, wl, step_fn, steps, warmup):
     elapsed = timed_leg(ranks, step_fn, steps, 0)
     wl.eng.profile = False
     return elapsed, wl.eng.collect_kernel_ms()
+
+
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(path, outputs):
+    """--dump-outputs: the arrays the last timed step handed back (rank 0's roots), as DIR/<name>.npy in float32.  Beyond 64 MB in all the
+    same fixed, seeded sample of roots is kept from every array, and their indices are written as DIR/root_index.npy (float64)."""
+    arrays = {k: v.detach().cpu().numpy().astype(np.float32) for k, v in outputs.items() if v is not None}
+    rows = next(iter(arrays.values())).shape[0]
+    row_bytes = sum(a.nbytes for a in arrays.values()) // max(rows, 1)
+    if rows * row_bytes > DUMP_LIMIT_BYTES:
+        keep = (DUMP_LIMIT_BYTES - 4096 * (len(arrays) + 1)) // (row_bytes + 8)     # room for the .npy headers and the float64 indices
+        idx = np.sort(np.random.default_rng(0).choice(rows, keep, replace=False))
+        arrays = {k: a[idx] for k, a in arrays.items()}
+        arrays["root_index"] = idx.astype(np.float64)
+    os.makedirs(path, exist_ok=True)
+    for k, a in arrays.items():
+        np.save(os.path.join(path, k + ".npy"), a)
 
 
 def other_runs(ranks, args, eq100, gp100, x_dom, x_bdy):
@@ -848,7 +870,11 @@ def main():
     main_step = sharding.step if by_samples else wl.step
 
     # ---- the timed region: W warm-up + K steps of the hot path, barrier + synchronize on both sides, MAX over ranks
-    elapsed, kernel_ms = measure(ranks, wl, main_step, args.steps, args.warmup)
+    last = {}
+
+    def step_keeping_outputs():
+        last["uz"], last["u_hat"] = main_step()
+    elapsed, kernel_ms = measure(ranks, wl, step_keeping_outputs if args.dump_outputs else main_step, args.steps, args.warmup)
     samples_leg = None
     if world > 1:
         t_other = timed_leg(ranks, wl.step if by_samples else sharding.step, args.steps, args.warmup)
@@ -862,6 +888,8 @@ def main():
     if rank != 0:
         ranks.close()
         return
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, last)
 
     # ---- accuracy on the harness protocol (untimed): 1000 + 200 test points
     exact = eq.exact_solution(xt_h)

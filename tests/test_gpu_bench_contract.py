@@ -6,6 +6,7 @@ import os
 import subprocess
 import sys
 
+import numpy as np
 import pytest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -143,3 +144,26 @@ def test_the_rccl_branches_execute_on_one_rank():
     assert j["backend"] == "nccl" and j["rccl_ranks"] == 1 and j["value"] > 0
     st = j["rccl_selftest"]
     assert st["ranks"] == 1 and st["unchanged"] and st["allreduce_ms"] > 0 and st["subgroup_allreduce"]
+
+
+@pytest.mark.gpu
+def test_dump_outputs_writes_the_last_timed_step_and_repeats_exactly(tmp_path):
+    """--dump-outputs DIR: after the K timed steps, the (uz, u_hat) the last one returned as float32 .npy files; the inputs are seeded,
+    so two runs with the same arguments write the same arrays."""
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1", "--batch", "256",
+           "--train-domain", "96", "--train-boundary", "32", "--no-cpu-baseline", "--no-other-runs", "--no-reference-logs-check",
+           "--no-gp-train-large"]
+    dumps = []
+    for k in range(2):
+        out = tmp_path / str(k)
+        r = subprocess.run(cmd + ["--dump-outputs", str(out)], capture_output=True, text=True, timeout=600, cwd=ROOT)
+        assert r.returncode == 0, r.stderr[-2000:]
+        j = json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][0])
+        assert j["steps"] == 3 and j["ms_per_step"] > 0
+        assert sorted(os.listdir(out)) == ["u_hat.npy", "uz.npy"]
+        dumps.append({name: np.load(out / (name + ".npy")) for name in ("uz", "u_hat")})
+    for got in dumps:
+        assert got["uz"].shape == (256, 101) and got["u_hat"].shape == (256,)
+        assert all(a.dtype == np.float32 and np.isfinite(a).all() for a in got.values())
+    for name in ("uz", "u_hat"):
+        np.testing.assert_array_equal(dumps[0][name], dumps[1][name])
