@@ -154,6 +154,27 @@ int scasml_picard_tree(const scasml_problem *prob_h, const scasml_plan *plan_h, 
                        float *points, const float *gp_vals,
                        float *out_uz, float *out_uhat, void *stream);
 
+/*
+ * Staged Picard tree, for equations whose f and g are not in the registry (the driver evaluates them as batched torch
+ * functions between launches; solvers/_picard.py).  A level-n solve runs SCASML_MODE_GENERATE of scasml_picard_tree once
+ * (its points do not depend on the equation), then stages S = 1 .. n, each computing the (u, z) of every level-S subtree
+ * from values the caller stored per tree site:
+ *   values : points_per_root x site_stride x 2 floats, site-major like `points`: (g, unused) at a terminal sample, (f+, f-) at
+ *            a node -- f at the node's point with the (u, z) of its level-l subtree ("+") and of its level-(l-1) subtree
+ *            ("-", l > 0 only), the lists of scasml_plan_stage_list.
+ *   entries: device int32 pairs (base site, origin site) of the level-S subtrees, from scasml_plan_stage_list
+ *            (SCASML_STAGE_SUBTREES); entries naming sites outside the tree are skipped.
+ *   uz     : S < n: points_per_root x site_stride x point_stride floats, site-major; the subtree with base site b writes its
+ *            clipped (z_1 .. z_d, u) to columns 0 .. d of row b * site_stride + root (the layout of a point row, u where t is).
+ *   out_uz : S = n: B x (1+d), (u, z) clipped -- what scasml_picard_tree computes for a registered equation.
+ * The arithmetic is that of SCASML_MODE_ACCUMULATE with f and g read from `values` (the quadrature nodes' X_k read back from
+ * `points`; the terminal normals and the full-history draws replayed from Philox), clipped at every level by prob.clip.
+ * prob.eq_id is not used.  Philox stream only: rng.flags must be 0 and rng.world 1.  B = 0 does nothing.
+ */
+int scasml_picard_stage(const scasml_problem *prob_h, const scasml_plan *plan_h, int32_t stage, const int32_t *entries,
+                        int64_t n_entries, int64_t B, int64_t site_stride, scasml_rng rng, const float *points,
+                        const float *values, float *uz, float *out_uz, void *stream);
+
 /* Clip all-reduced partial sums in place (world > 1): MLP.py:272-274 / ScaSML.py:281-284. */
 int scasml_clip(float *uz, int64_t count, float clip, void *stream);
 /* The same followed, when round16 != 0, by the root call's .astype(float16) (MLP.py:274, ScaSML.py:284, MLP_full_history.py:180 --
@@ -270,6 +291,19 @@ int scasml_plan_site_kinds(const scasml_plan *plan_h, int32_t rank, int32_t worl
  * Returns the number of units (<0 on error); fills owner_h[0 .. units) (needs capacity >= units, world <= 255) and, if not NULL,
  * load_h[0 .. world) with the cost dealt to every rank.  Philox is keyed by tree site, so the sum over ranks does not depend on the dealing. */
 int32_t scasml_plan_deal_units(const scasml_plan *plan_h, int32_t world, const double *site_cost_h, uint8_t *owner_h, int32_t capacity, double *load_h);
+
+/* Host helper: the schedule of a staged solve (scasml_picard_stage), in the order of scasml_plan_site_kinds' enumeration.
+ *   SCASML_STAGE_SUBTREES, stage S in 1..n : pairs (base site, origin site) of every level-S subtree of the tree; the root call
+ *                                             is (0, points_per_root - 1).
+ *   SCASML_STAGE_TERMINALS, stage 0        : every terminal sample site (where g is needed).
+ *   SCASML_STAGE_F_AFTER, stage S in 0..n-1: triples (node site, child base site, slot) of the f evaluations that become possible
+ *                                             once the level-S subtrees are known: slot 0 ("+") for every node of a level-S term,
+ *                                             slot 1 ("-") for every node of a level-(S+1) term.  Stage 0: the children are
+ *                                             level-0 subtrees, whose (u, z) is zero.
+ * out_h NULL: returns the number of entries; otherwise fills out_h (capacity in entries, >= that number) and returns it.
+ * < 0 on error (n outside 1..SCASML_MAX_LEVEL, stage out of range, terms inconsistent with plan.sites). */
+enum { SCASML_STAGE_SUBTREES = 0, SCASML_STAGE_TERMINALS = 1, SCASML_STAGE_F_AFTER = 2 };
+int64_t scasml_plan_stage_list(const scasml_plan *plan_h, int32_t kind, int32_t stage, int32_t *out_h, int64_t capacity);
 
 /* Host only: the workgroup -> tile map of the 128 x 128 FP64 update kernels (the trailing update of scasml_cholesky, the substitution
  * updates of scasml_cholesky_inverse / scasml_trsm_*, scasml_gemm_nt_sub; models/GP.py:260-267, 599 are what they replace).  Workgroups

@@ -14,6 +14,7 @@ MODE_MLP, MODE_GENERATE, MODE_ACCUMULATE = 0, 1, 2
 RNG_COMPAT_CRN = 1
 RNG_COMPAT_F16 = 2
 RNG_JAX_STREAM = 4
+STAGE_SUBTREES, STAGE_TERMINALS, STAGE_F_AFTER = 0, 1, 2      # scasml_plan_stage_list kinds
 EQ_GRAD_DEPENDENT_NONLINEAR = 0
 EQ_CUBIC_REACTION_DIFFUSION = 1
 EQ_QUADRATIC_GRADIENT_REACTION_DIFFUSION = 2      # f(u, sum z, |z|^2): surrogate-free Picard kernels only
@@ -63,6 +64,8 @@ SIGNATURES = {
     "scasml_point_stride": (C.c_int32, [C.c_int32]),
     "scasml_picard_tree": (C.c_int, [C.POINTER(Problem), C.POINTER(Plan), C.c_int, C.c_void_p, C.c_int64, C.c_int64, Rng,
                                      C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "scasml_picard_stage": (C.c_int, [C.POINTER(Problem), C.POINTER(Plan), C.c_int32, C.c_void_p, C.c_int64, C.c_int64, C.c_int64, Rng,
+                                      C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "scasml_clip": (C.c_int, [C.c_void_p, C.c_int64, C.c_float, C.c_void_p]),
     "scasml_clip_round16": (C.c_int, [C.c_void_p, C.c_int64, C.c_float, C.c_int32, C.c_void_p]),
     "scasml_debug_normals": (C.c_int, [Rng, C.c_uint32, C.c_int32, C.c_int64, C.c_void_p, C.c_void_p]),
@@ -77,6 +80,7 @@ SIGNATURES = {
     "scasml_gp_eval": (C.c_int, [C.POINTER(GpModel), C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p]),
     "scasml_gp_eval_sites": (C.c_int, [C.POINTER(GpModel), C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p]),
     "scasml_plan_site_kinds": (C.c_int, [C.POINTER(Plan), C.c_int32, C.c_int32, C.c_void_p, C.c_void_p]),
+    "scasml_plan_stage_list": (C.c_int64, [C.POINTER(Plan), C.c_int32, C.c_int32, C.c_void_p, C.c_int64]),
     "scasml_plan_deal_units": (C.c_int32, [C.POINTER(Plan), C.c_int32, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p]),
     "scasml_tile_order_blocks": (C.c_int64, [C.c_int64, C.c_int64, C.c_int32]),
     "scasml_tile_order": (C.c_int, [C.c_int64, C.c_int64, C.c_int64, C.c_int32, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),

@@ -199,6 +199,78 @@ extern "C" int scasml_plan_site_kinds(const scasml_plan *plan_h, int32_t rank, i
     return 0;
 }
 
+// The staged walk of a level-n tree (scasml_picard_stage): the same enumeration as site_kinds_rec, collecting per stage what the driver
+// gathers for the torch callbacks.  A subtree of level L >= 1 is named by its base site (its first terminal sample); its origin is the node
+// just before it, or the root row (site sites[n]) for the root call.
+namespace {
+struct StageWalk {
+    const scasml_plan *p;
+    int32_t kind, stage;
+    int32_t *out;       // NULL: count only
+    int64_t cap, count;
+    void emit(int32_t a, int32_t b, int32_t c) {
+        const int w = kind == SCASML_STAGE_TERMINALS ? 1 : (kind == SCASML_STAGE_SUBTREES ? 2 : 3);
+        if (out && count < cap) {
+            int32_t *e = out + count * w;
+            e[0] = a;
+            if (w > 1) e[1] = b;
+            if (w > 2) e[2] = c;
+        }
+        ++count;
+    }
+    // returns the number of sites of the subtree (to check plan.sites against its terms)
+    int64_t rec(int L, int64_t base, int64_t origin) {
+        if (L == 0) return 0;
+        if (kind == SCASML_STAGE_SUBTREES && L == stage) emit((int32_t)base, (int32_t)origin, 0);
+        for (int m = 0; m < p->mg[L]; ++m)
+            if (kind == SCASML_STAGE_TERMINALS) emit((int32_t)(base + m), 0, 0);
+        int64_t o = p->mg[L];
+        for (int l = 0; l < L; ++l) {
+            const scasml_term &t = p->term[L][l];
+            for (int m = 0; m < t.mc; ++m)
+                for (int k = 0; k < t.q; ++k) {
+                    const int64_t node = base + o;
+                    o += 1;
+                    if (kind == SCASML_STAGE_F_AFTER && l == stage) emit((int32_t)node, (int32_t)(base + o), 0);
+                    o += rec(l, base + o, node);
+                    if (l > 0) {
+                        if (kind == SCASML_STAGE_F_AFTER && l == stage + 1) emit((int32_t)node, (int32_t)(base + o), 1);
+                        o += rec(l - 1, base + o, node);
+                    }
+                }
+        }
+        return o;
+    }
+};
+}  // namespace
+
+extern "C" int64_t scasml_plan_stage_list(const scasml_plan *plan_h, int32_t kind, int32_t stage, int32_t *out_h, int64_t capacity) {
+    if (!plan_h || plan_h->n < 1 || plan_h->n > SCASML_MAX_LEVEL) return fail(SCASML_ERR_ARG, "plan_stage_list: bad plan (n must be 1..%d)", SCASML_MAX_LEVEL);
+    const int n = plan_h->n;
+    if (kind == SCASML_STAGE_SUBTREES) {
+        if (stage < 1 || stage > n) return fail(SCASML_ERR_ARG, "plan_stage_list: subtrees of stage %d outside 1..%d", stage, n);
+    } else if (kind == SCASML_STAGE_TERMINALS) {
+        if (stage != 0) return fail(SCASML_ERR_ARG, "plan_stage_list: the terminal list takes stage 0, got %d", stage);
+    } else if (kind == SCASML_STAGE_F_AFTER) {
+        if (stage < 0 || stage >= n) return fail(SCASML_ERR_ARG, "plan_stage_list: f-list after stage %d outside 0..%d", stage, n - 1);
+    } else {
+        return fail(SCASML_ERR_ARG, "plan_stage_list: unknown kind %d", kind);
+    }
+    if (capacity < 0) return fail(SCASML_ERR_ARG, "plan_stage_list: negative capacity");
+    for (int np = 1; np <= n; ++np)
+        for (int l = 0; l < np; ++l)
+            if (plan_h->term[np][l].q < 1 || plan_h->term[np][l].q > SCASML_MAX_Q || plan_h->term[np][l].mc < 1)
+                return fail(SCASML_ERR_ARG, "plan_stage_list: bad term [%d][%d]", np, l);
+    // count first: the sites must agree with plan.sites before anything is written
+    StageWalk w{plan_h, kind, stage, nullptr, 0, 0};
+    if (w.rec(n, 0, plan_h->sites[n]) != plan_h->sites[n]) return fail(SCASML_ERR_ARG, "plan_stage_list: plan.sites is inconsistent with its terms");
+    if (!out_h) return w.count;
+    if (capacity < w.count) return fail(SCASML_ERR_ARG, "plan_stage_list: %lld entries, capacity %lld", (long long)w.count, (long long)capacity);
+    StageWalk f{plan_h, kind, stage, out_h, capacity, 0};
+    f.rec(n, 0, plan_h->sites[n]);
+    return f.count;
+}
+
 extern "C" int32_t scasml_point_stride(int32_t d) { return (d + 4 + 15) / 16 * 16; }
 
 // The tile order of the 128 x 128 FP64 update kernels (host_common.hpp), for inspection and the CPU tests

@@ -4,8 +4,10 @@
     u_t + mu sum_i d_i u + sigma^2/2 Lap u + f(u, sum_i z_i) = 0,  z = sigma grad u,  u(T) = g,   mu, sigma constant,
 through an equation registry (``eq_id``; device functors in csrc/equations.hpp): the reference's concrete
 ``Grad_Dependent_Nonlinear`` (:232-417) is id 0 and ``Cubic_Reaction_Diffusion`` (no reference counterpart) id 1.  The
-methods here are the host-side view of the same formulas (NumPy, for the harness metric and the GP boundary data); a
-subclass that sets no ``eq_id`` has no kernels and the solvers refuse it.  deepxde is
+methods here are the host-side view of the same formulas (NumPy, for the harness metric and the GP boundary data).
+A subclass that sets no ``eq_id`` may instead set ``torch_callbacks = True``: its own ``f`` and ``g``, batched torch functions,
+then drive MLP and MLP_full_history through the staged Picard tree (the contract is in the ``Equation`` docstring; ScaSML and
+the GP fit stay registry-only).  A subclass with neither has no kernels and the solvers refuse it.  deepxde is
 not a dependency: ``geometry()`` records the box and the samplers are NumPy restatements of
 ``GeometryXTime.random_points / random_boundary_points``.
 """
@@ -24,8 +26,30 @@ class _Box:
 
 class Equation(object):
     """Abstract PDE  u_t + mu.grad u + sigma^2/2 Lap u + f(u, sigma grad u) = 0, u(T) = g
-    (equations/equations.py:15-230)."""
-    eq_id = None           # kernels exist only for subclasses that set this
+    (equations/equations.py:15-230).
+
+    Two ways to run a subclass on the device:
+
+    * ``eq_id`` set: f and g are the registry's device functors (csrc/equations.hpp), fused into the Picard tree kernels; every
+      solver (MLP, MLP_full_history, ScaSML, ScaSML_full_history) and the GP fit accept it.
+    * ``eq_id = None`` and ``torch_callbacks = True``: MLP and MLP_full_history call the subclass's own ``f(x_t, u, z)`` and
+      ``g(x_t)`` between the launches of the staged Picard tree (csrc/picard_staged.hip).  The callback contract:
+
+      - ``f`` receives ``x_t (R, d+1)``, ``u (R, 1)``, ``z (R, d)``; ``g`` receives ``x_t (R, d+1)`` whose time column is ``T``.
+        All are contiguous float32 tensors on the current CUDA device.
+      - Both return ``(R, 1)`` or ``(R,)`` float32 on the same device; anything else raises ``ValueError`` naming the function.
+      - Calls are whole batches: ``g`` once per root chunk, ``f`` exactly ``n`` times per root chunk, however large ``B`` and the
+        Monte-Carlo sample counts are -- so both must be vectorised over rows.  ``n == 0`` and ``B == 0`` call neither.
+      - Non-finite values flow through as in the fused kernels.
+      - ``mu()`` and ``sigma()`` must return scalars (constant drift and volatility), else ``ValueError``.  ``norm_estimation``
+        is the clipping bound, ``geometry()`` sets ``T``.
+      - Refused with ``NotImplementedError``: ScaSML / ScaSML_full_history and ``GP.GPsolver`` (the collocation operator needs
+        ``f_parts``), ``reference_mode``, ``compat_rng="jax"``, ``compat_f16``, ``compat_crn`` and sample-sharded solves.
+
+    * Neither: the solvers refuse the equation with ``NotImplementedError``.
+    """
+    eq_id = None             # registry id of the fused kernels (csrc/equations.hpp)
+    torch_callbacks = False  # eq_id None and this True: f and g are batched torch functions (staged Picard tree)
 
     def __init__(self, n_input, n_output=1):
         self.n_input = n_input

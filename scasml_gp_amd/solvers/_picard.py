@@ -9,6 +9,9 @@ from .. import _lib, tables
 
 # cap on the point buffer of one ScaSML chunk (bytes); larger batches are walked in root chunks
 POINT_BUFFER_BYTES = 24 << 30
+# cap on what one root chunk of a staged solve (equations with torch f and g) holds at once: the point buffer, the uz buffer in the same
+# layout, the per-site values and the gathered inputs of the largest callback (bytes); larger batches are walked in root chunks
+STAGED_BUFFER_BYTES = 24 << 30
 
 
 def _as_device(x_t, torch):
@@ -26,7 +29,10 @@ class PicardEngine:
             # ONE switch for "what the reference's solver objects compute": its random stream under its key schedule and its solver-level
             # float16 casts (the surrogate's half of it is GP(compat="reference"), the default)
             compat_rng, compat_f16 = "jax", True
-        if getattr(equation, "eq_id", None) is None:
+        # eq_id unset and torch_callbacks true: f and g are the equation's own batched torch functions, called between the launches of the
+        # staged tree (_solve_staged); an equation with neither has no kernels
+        self.callbacks = getattr(equation, "eq_id", None) is None and bool(getattr(equation, "torch_callbacks", False))
+        if getattr(equation, "eq_id", None) is None and not self.callbacks:
             raise NotImplementedError("no HIP kernels for equation %s (eq_id unset)" % type(equation).__name__)
         if getattr(equation, "surrogate_free_only", False) and (gp is not None or reference_mode or compat_rng == "jax"):
             raise NotImplementedError("equation %s has an f of |z|^2: its kernels are the surrogate-free Picard tree on the Philox stream (MLP, MLP_full_history); "
@@ -45,6 +51,16 @@ class PicardEngine:
         if compat_rng not in (None, "jax"):
             raise ValueError("compat_rng must be None or 'jax'")
         self.compat_rng = compat_rng
+        if self.callbacks:
+            name = type(equation).__name__
+            if gp is not None:
+                raise NotImplementedError("equation %s has torch callbacks: ScaSML needs its f_parts for the GP's collocation operator and the "
+                                          "surrogate's full gradient at every tree site; use MLP or MLP_full_history" % name)
+            if compat_rng is not None or compat_f16 or compat_crn:
+                raise NotImplementedError("equation %s has torch callbacks: the staged tree runs on the Philox stream only (no reference_mode, "
+                                          "compat_rng, compat_f16 or compat_crn)" % name)
+            for what in ("mu", "sigma"):
+                _scalar_of(equation, what)
         self.jax_key = (0, 0)
         self.jax_splits = 0
         self.calls = 0                 # Philox stream id: advances once per uz_solve (E-9)
@@ -144,8 +160,13 @@ class PicardEngine:
     def problem(self):
         eq = self.equation
         p = _lib.Problem()
-        p.d, p.eq_id = eq.n_input - 1, eq.eq_id
-        p.T, p.mu, p.sigma = float(eq.T), float(eq.mu()), float(eq.sigma())
+        # a callback equation has no id: its Problem goes to GENERATE (which evaluates neither f nor g, so any registered id gives the same
+        # points) and to scasml_picard_stage (which reads no id)
+        p.d, p.eq_id = eq.n_input - 1, (_lib.EQ_GRAD_DEPENDENT_NONLINEAR if self.callbacks else eq.eq_id)
+        if self.callbacks:
+            p.T, p.mu, p.sigma = float(eq.T), _scalar_of(eq, "mu"), _scalar_of(eq, "sigma")
+        else:
+            p.T, p.mu, p.sigma = float(eq.T), float(eq.mu()), float(eq.sigma())
         p.clip = float(eq.uncertainty if self.gp is not None else eq.norm_estimation)
         return p
 
@@ -158,6 +179,8 @@ class PicardEngine:
         if x.dim() != 2 or x.shape[1] != d + 1:
             raise ValueError("x_t must have shape (batch, %d), got %s" % (d + 1, tuple(x.shape)))
         B = x.shape[0]
+        if self.callbacks and world > 1:
+            raise NotImplementedError("equation %s has torch callbacks: a staged solve is not sample-sharded" % type(self.equation).__name__)
         plan, prob = self.plan(n, par), self.problem()
         if self.gp is not None and float(getattr(self.gp, "T", self.equation.T)) != float(self.equation.T):
             # the GP folds its terminal time into packed row constants (site kind 3); the tree emits terminal points at the equation's T
@@ -179,6 +202,9 @@ class PicardEngine:
             self.calls += 1
         out = torch.empty((B, d + 1), dtype=torch.float32, device="cuda")
         s = _lib.stream_ptr()
+        if self.callbacks:
+            self._solve_staged(n, par, plan, prob, x, out, rng, s)
+            return out, None, was_numpy
         if self.gp is None:
             _lib.check(self._timed("picard_mlp", lambda: lib.scasml_picard_tree(
                 C.byref(prob), C.byref(plan), _lib.MODE_MLP, _lib.ptr(x), B, 0, rng, None, None, _lib.ptr(out), None, s)), "picard_tree")
@@ -216,6 +242,101 @@ class PicardEngine:
                 uhat[b0:b0 + nb] = self.gp._predict_device(xc)[:, 0]
         self._jax_commit(jax_next, stream_id)
         return out, uhat, was_numpy
+
+    def stage_lists(self, n, par):
+        """Device lists of a staged solve (scasml_plan_stage_list), uploaded once per plan: int32 (base, origin) pairs per stage 1..n for
+        the stage kernel, int64 site / child-base / slot columns for the gathers and scatters around the callbacks."""
+        key = ("stages", n, par)
+        if key not in self._kinds:
+            torch = _lib.require_gpu()
+            h = tables.stage_lists(self.plan(n, par))
+            dev = lambda a: torch.from_numpy(np.ascontiguousarray(a)).cuda()
+            self._kinds[key] = {
+                "subtrees": {S: dev(v) for S, v in h["subtrees"].items()},
+                "terminals": dev(h["terminals"].astype(np.int64)),
+                "f_after": {S: tuple(dev(v[:, j].astype(np.int64)) for j in range(3)) for S, v in h["f_after"].items()},
+                "widest": max([len(h["terminals"])] + [len(v) for v in h["f_after"].values()]),
+            }
+        return self._kinds[key]
+
+    def _callback(self, name, fn, args, rows):
+        """Call the equation's f or g on one batch and check what comes back: float32 (rows, 1) or (rows,) on the inputs' device."""
+        torch = _lib.require_gpu()
+        r = self._timed("callback_" + name, lambda: fn(*args))
+        if not (isinstance(r, torch.Tensor) and r.dtype == torch.float32 and r.device == args[0].device and tuple(r.shape) in ((rows, 1), (rows,))):
+            got = ("%s of shape %s on %s" % (r.dtype, tuple(r.shape), r.device)) if isinstance(r, torch.Tensor) else type(r).__name__
+            raise ValueError("%s.%s must return a float32 tensor of shape (%d, 1) or (%d,) on %s; got %s"
+                             % (type(self.equation).__name__, name, rows, rows, args[0].device, got))
+        return r.reshape(rows)
+
+    def _solve_staged(self, n, par, plan, prob, x, out, rng, s):
+        """A solve for an equation with torch f and g, per root chunk: GENERATE every tree point; g on the terminal samples; then for
+        S = 0 .. n-1 the stage-S kernel (S >= 1: the (u, z) of every level-S subtree) followed by f on every node whose child is now
+        known; the stage-n kernel writes ``out``.  Gathers and scatters are device indexing with the cached lists (stage_lists)."""
+        torch = _lib.require_gpu()
+        lib = _lib.load()
+        eq = self.equation
+        B, d = x.shape[0], x.shape[1] - 1
+        if n == 0 or B == 0:                   # MLP.py:205-207: zeros, no callback
+            out.zero_()
+            return
+        lists = self.stage_lists(n, par)
+        ppr = int(lib.scasml_points_per_root(C.byref(plan)))
+        kp = int(lib.scasml_point_stride(d))
+        # per root: points and uz (kp floats per site each), values (2 per site), and the widest callback's gathered x_t, u, z and result
+        per_root = 4 * (2 * ppr * kp + 2 * ppr + lists["widest"] * (2 * d + 3))
+        chunk = max(1, min(B, STAGED_BUFFER_BYTES // per_root))
+        pts, uzb, vals = self._staged_buffers(chunk * ppr, kp)
+        P, U, V = pts.view(ppr, chunk, kp), uzb.view(ppr, chunk, kp), vals.view(ppr, chunk, 2)
+        term = lists["terminals"]
+        for b0 in range(0, B, chunk):
+            nb = min(chunk, B - b0)
+            rng_c = _lib.Rng(rng.seed, rng.stream, rng.root0 + b0, 0, 1, 0, 0, None, None)   # root0 + b0: normals independent of the chunking
+            xc = x[b0:b0 + nb]
+            _lib.check(self._timed("picard_staged_generate", lambda: lib.scasml_picard_tree(
+                C.byref(prob), C.byref(plan), _lib.MODE_GENERATE, _lib.ptr(xc), nb, chunk, rng_c, _lib.ptr(pts), None, None, None, s)),
+                "picard_tree(generate)")
+            xg = self._timed("picard_staged_gather", lambda: P[term, :nb, :d + 1].reshape(-1, d + 1).contiguous())
+            gv = self._callback("g", eq.g, (xg,), xg.shape[0])
+
+            def scatter_g():
+                V[term, :nb, 0] = gv.view(-1, nb)
+            self._timed("picard_staged_scatter", scatter_g)
+            for S in range(n):
+                if S >= 1:
+                    self._stage(S, prob, plan, lists, nb, chunk, rng_c, pts, vals, uzb, None, s)
+                node, child, slot = lists["f_after"][S]
+                rows = node.shape[0] * nb
+
+                def gather():
+                    xf = P[node, :nb, :d + 1].reshape(rows, d + 1).contiguous()
+                    if S == 0:                 # the children are level-0 calls: (u, z) = 0 (MLP.py:205-207)
+                        return xf, torch.zeros((rows, 1), dtype=torch.float32, device=x.device), torch.zeros((rows, d), dtype=torch.float32, device=x.device)
+                    # a uz row is (z_1 .. z_d, u): each gathered straight into its own contiguous tensor
+                    return xf, U[child, :nb, d].reshape(rows, 1).contiguous(), U[child, :nb, :d].reshape(rows, d).contiguous()
+                args = self._timed("picard_staged_gather", gather)
+                fv = self._callback("f", eq.f, args, rows)
+
+                def scatter():
+                    V[node, :nb, slot] = fv.view(-1, nb)
+                self._timed("picard_staged_scatter", scatter)
+            self._stage(n, prob, plan, lists, nb, chunk, rng_c, pts, vals, uzb, out[b0:b0 + nb], s)
+
+    def _stage(self, S, prob, plan, lists, nb, stride, rng, pts, vals, uzb, out, s):
+        lib = _lib.load()
+        ent = lists["subtrees"][S]
+        _lib.check(self._timed("picard_staged_stage%d" % S, lambda: lib.scasml_picard_stage(
+            C.byref(prob), C.byref(plan), S, _lib.ptr(ent), ent.shape[0], nb, stride, rng, _lib.ptr(pts), _lib.ptr(vals),
+            _lib.ptr(uzb), _lib.ptr(out), s)), "picard_stage")
+
+    def _staged_buffers(self, rows, kp):
+        """Point, uz and value buffers of a staged solve, site-major, kept across calls like _buffers."""
+        torch = _lib.require_gpu()
+        have = self._work.get("staged")
+        if have is None or have[0].shape[0] < rows or have[0].shape[1] != kp:
+            self._work.pop("staged", None)
+            self._work["staged"] = tuple(torch.zeros((rows, w), dtype=torch.float32, device="cuda") for w in (kp, kp, 2))
+        return tuple(b[:rows] for b in self._work["staged"])
 
     def _root_bound(self, x, x_max, own):
         """Largest |coordinate| of the roots: given for host arrays; reduced on the device otherwise.  The reduction (and the read it ends
@@ -310,6 +431,17 @@ def deal_units(plan, world, cost=None):
     if got != units:
         raise _lib.ScasmlError("plan_deal_units failed (%d): %s" % (got, lib.scasml_last_error().decode()))
     return owner[:units].copy(), load
+
+
+def _scalar_of(equation, what):
+    """equation.mu() / .sigma() as a float: the kernels take constant drift and volatility; anything but a scalar is refused."""
+    v = getattr(equation, what)()
+    if hasattr(v, "detach"):              # a torch tensor
+        v = v.detach().cpu().numpy()
+    a = np.asarray(v)
+    if a.ndim != 0 or a.dtype.kind not in "biuf":
+        raise ValueError("%s.%s() must return a scalar (constant %s), got %r" % (type(equation).__name__, what, what, v))
+    return float(a)
 
 
 def deliver(t, was_numpy):

@@ -182,3 +182,28 @@ def reference_evaluation_count(variant, n, par, scasml, T=0.5):
                 c += q * (rec(l - 1) + inc + extra)
         return c
     return rec(n)
+
+
+def stage_list(plan, kind, stage):
+    """One list of scasml_plan_stage_list as an int32 array: (E, 2) (base site, origin site) for ``_lib.STAGE_SUBTREES``, (E,) sites for
+    ``_lib.STAGE_TERMINALS``, (E, 3) (node site, child base site, slot) for ``_lib.STAGE_F_AFTER``."""
+    import ctypes as C
+    lib = _lib.load()
+    width = {_lib.STAGE_SUBTREES: 2, _lib.STAGE_TERMINALS: 1, _lib.STAGE_F_AFTER: 3}[kind]
+    count = lib.scasml_plan_stage_list(C.byref(plan), kind, stage, None, 0)
+    if count < 0:
+        raise _lib.ScasmlError("plan_stage_list failed (%d): %s" % (count, lib.scasml_last_error().decode()))
+    out = np.zeros((count, width), dtype=np.int32)
+    got = lib.scasml_plan_stage_list(C.byref(plan), kind, stage, out.ctypes.data_as(C.c_void_p), count)
+    if got != count:
+        raise _lib.ScasmlError("plan_stage_list failed (%d): %s" % (got, lib.scasml_last_error().decode()))
+    return out[:, 0] if width == 1 else out
+
+
+def stage_lists(plan):
+    """The whole schedule of a staged solve of ``plan`` (n >= 1): {"subtrees": {S: (E, 2)} for S = 1..n, "terminals": (E,),
+    "f_after": {S: (E, 3)} for S = 0..n-1}."""
+    n = int(plan.n)
+    return {"subtrees": {S: stage_list(plan, _lib.STAGE_SUBTREES, S) for S in range(1, n + 1)},
+            "terminals": stage_list(plan, _lib.STAGE_TERMINALS, 0),
+            "f_after": {S: stage_list(plan, _lib.STAGE_F_AFTER, S) for S in range(n)}}
