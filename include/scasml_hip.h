@@ -329,7 +329,8 @@ int scasml_gp_gram(int32_t d, double a, const float *x_dom, int32_t n_dom, const
 int scasml_cholesky(double *A, int64_t M, double nugget, int32_t *info_dev, void *stream);
 
 /* Solve L X = B (trans=0) or L^T X = B (trans=1) in place; L lower M x M, B M x nrhs row-major
- * float64: the solves of models/GP.py:439, 533, 599. */
+ * float64: the solves of models/GP.py:439, 533, 599.  nrhs < 2^21 (2097152): larger counts return
+ * SCASML_ERR_UNSUPPORTED (nrhs is the row stride of the update tiles, addressed with 32-bit offsets). */
 int scasml_trsm_lower(const double *L, int64_t M, double *Bmat, int64_t nrhs, int trans, void *stream);
 
 /* A = (L L^T)^-1 from the lower Cholesky factor L (M x M float64, M a multiple of 32; A is overwritten, any

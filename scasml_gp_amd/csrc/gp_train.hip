@@ -136,8 +136,8 @@ __device__ __forceinline__ void mfma_tile_accumulate(const double (*As)[LDP], co
 }
 
 // Output-tile addressing: ONE 32-bit byte offset per thread -- its place (row wr + l4, column wc + l15) inside the tile; tile rows < 128 and
-// ldc < 2^21, so below 2^32 bytes -- against a scalar base per (i, j, e) fragment element: the accesses take the SGPR-base form and no 64-bit
-// address lives in a VGPR (sixteen of them, hoisted out of the tile loop, spilled in the streamed kernel).
+// ldc < 2^21 (M <= 65535 * 32 in the factorisation and the inverse; scasml_trsm_lower refuses nrhs >= 2^21), so below 2^32 bytes -- against a
+// scalar base per (i, j, e) fragment element: the accesses take the SGPR-base form and no 64-bit address lives in a VGPR (sixteen of them, hoisted out of the tile loop, spilled in the streamed kernel).
 template <int NT, int WS = 2>
 __device__ __forceinline__ uint32_t tile_thread_offset(int64_t ldc) {
     const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
@@ -893,6 +893,8 @@ extern "C" int scasml_trsm_lower(const double *L, int64_t M, double *Bmat, int64
     if (nrhs == 0) return 0;
     if (M % NB) return fail(SCASML_ERR_UNSUPPORTED, "trsm: M=%lld is not a multiple of %d", (long long)M, NB);
     if (M > 65535 * (int64_t)NB) return fail(SCASML_ERR_UNSUPPORTED, "trsm: M too large for this build");
+    // nrhs is the leading dimension of the update tiles, whose per-thread offsets are 32-bit (tile_thread_offset: ldc < 2^21)
+    if (nrhs >= ((int64_t)1 << 21)) return fail(SCASML_ERR_UNSUPPORTED, "trsm: nrhs=%lld is not below 2^21 (2097152), the bound of the update tiles", (long long)nrhs);
     hipStream_t s = (hipStream_t)stream;
     const unsigned cb = (unsigned)((nrhs + 255) / 256), ct = (unsigned)((nrhs + TB - 1) / TB);
     // two-level blocked substitution (see scasml_cholesky): NB rows at a time inside a group of kOuterRows rows, then

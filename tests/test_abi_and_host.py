@@ -457,3 +457,14 @@ def test_round2_entry_points_validate_their_arguments_without_a_gpu(lib):
     plan = tables.build_plan("quad", 1, 1, 0.5, True)
     assert lib.scasml_picard_tree(C.byref(prob), C.byref(plan), 0, p8, 4, 3, _lib.Rng(0, 0, 0, 0, 1, 0, 0), None, None, p8, None, None) == -1
     assert b"site_stride" in lib.scasml_last_error()
+
+
+def test_trsm_lower_refuses_right_hand_side_counts_its_tiles_cannot_address(lib):
+    """nrhs is the row stride of scasml_trsm_lower's update tiles, whose per-thread offsets are 32-bit: from 2^21 columns on the entry refuses
+    (rows 64-127 of a tile would wrap onto other rows of B without a fault) instead of launching."""
+    p8 = C.c_void_p(8)
+    for nrhs in (1 << 21, 1 << 24):
+        for trans in (0, 1):
+            assert lib.scasml_trsm_lower(p8, 96, p8, nrhs, trans, None) == -2
+            assert b"2^21" in lib.scasml_last_error()
+    assert lib.scasml_trsm_lower(p8, 96, p8, 0, 0, None) == 0                          # no right-hand sides: nothing to do
