@@ -18,6 +18,13 @@ STAGE_SUBTREES, STAGE_TERMINALS, STAGE_F_AFTER = 0, 1, 2      # scasml_plan_stag
 EQ_GRAD_DEPENDENT_NONLINEAR = 0
 EQ_CUBIC_REACTION_DIFFUSION = 1
 EQ_QUADRATIC_GRADIENT_REACTION_DIFFUSION = 2      # f(u, sum z, |z|^2): surrogate-free Picard kernels only
+# round16 bits of the as-coded GP entry points (include/scasml_hip.h); bit 2 means one thing for the Gram, Gram rows, cross rows and
+# float64 evaluation, another for the matrix-core evaluation
+ROUND16_ENTRIES = 1       # every kernel entry rounded to float16
+ROUND16_OUTPUTS = 2       # evaluation: u_hat and eps_PDE leave as float16 values
+ROUND16_F16_OPS = 4       # Gram, Gram rows, cross rows, float64 evaluation: the float16 op sequence on float16 rows
+ROUND16_ONE_PLANE = 4     # matrix-core evaluation, ROUND16_ENTRIES off: the evaluation point as one float16 plane
+ROUND16_F16_LAP = 8       # exploratory, with ROUND16_F16_OPS: the Hutchinson Laplacian blocks in the float16 op sequence too
 
 
 class Problem(C.Structure):

@@ -126,16 +126,14 @@ def owned_blocks(nblk, rank, world):
 class DistCholesky:
     """K(phi, phi) + nugget I, block-row distributed: build(), factor(), solve(b)."""
 
-    def __init__(self, d, a, x_dom, x_bdy, nugget, comm=None, compat_idx=None, round_diag=False, f16_graph=False, f16_extra=0):
+    def __init__(self, d, a, x_dom, x_bdy, nugget, comm=None, compat_idx=None, round_diag=False, gram_bits=_lib.ROUND16_ENTRIES):
         """compat_idx: the five Hutchinson indices -> the Gram AS CODED by the reference (shifted blocks, float16 entries:
-        scasml_gp_gram_compat_rows); round_diag: the diagonal of K + nugget I rounded to float16 as well, i.e. the matrix
-        kernel_phi_phi_perturb.astype(float16) of models/GP.py:268 that the right_vector solve of :599 uses."""
+        scasml_gp_gram_compat_rows, whose round16 is ``gram_bits``: GP._gram_bits); round_diag: the diagonal of K + nugget I rounded to
+        float16 as well, i.e. the matrix kernel_phi_phi_perturb.astype(float16) of models/GP.py:268 that the right_vector solve of :599 uses."""
         torch = _lib.require_gpu()
         self.compat_idx = None if compat_idx is None else np.ascontiguousarray(np.asarray(compat_idx, dtype=np.int32))
         self.round_diag = bool(round_diag)
-        # scasml_gp_gram_compat_rows: bit 2 = the float16 op sequence on float16 rows (GP(f16_graph=True)); f16_extra = the GP's exploratory bit 3 --
-        # the same mask GP.kernel_phi_phi builds, so the distributed and the single-GPU Gram cannot differ
-        self.gram_bits = 1 | ((4 | int(f16_extra)) if f16_graph else 0)
+        self.gram_bits = int(gram_bits)
         self.lib = _lib.load()
         self.comm = comm or Comm()
         self.d, self.a, self.nugget = int(d), float(a), float(nugget)
@@ -494,11 +492,8 @@ class DistributedGP:
         gp = self.gp
         eq_id, d, sig, mu = int(gp.equation.eq_id), int(gp.d), float(gp.equation.sigma()), float(gp.equation.mu())
         compat_idx = gp.laplacian_idx if getattr(gp, "compat", None) == "reference" else None
-        xd16, xb16 = np.asarray(x_t_domain, dtype=np.float32), np.asarray(x_t_boundary, dtype=np.float32)
-        graph = bool(getattr(gp, "f16_graph", False)) and compat_idx is not None and \
-            np.array_equal(xd16.astype(np.float16).astype(np.float32), xd16) and np.array_equal(xb16.astype(np.float16).astype(np.float32), xb16)
-        ch = DistCholesky(d, 1.0 / float(gp.sigma) ** 2, x_t_domain, x_t_boundary, gp.nugget, self.comm, compat_idx=compat_idx, f16_graph=graph,
-                          f16_extra=getattr(gp, "_f16_extra", 0)).build().factor()
+        gram_bits = gp._gram_bits(np.asarray(x_t_domain, dtype=np.float32), np.asarray(x_t_boundary, dtype=np.float32))   # the single-GPU Gram's mask
+        ch = DistCholesky(d, gp.a, x_t_domain, x_t_boundary, gp.nugget, self.comm, compat_idx=compat_idx, gram_bits=gram_bits).build().factor()
         self.chol = ch
         N, Nb, M = ch.n_dom, ch.n_bdy, ch.M
         bdy_g = torch.as_tensor(np.asarray(gp.bdy_g(np.asarray(x_t_boundary)), dtype=np.float64), device="cuda").contiguous()
@@ -584,8 +579,8 @@ class DistributedGP:
             panel, ch.R = ch.R, None
             ch.diag, ch.ninv, ch._scratch = [None] * ch.nblk, None, None
             torch.cuda.empty_cache()
-            ch2 = DistCholesky(d, 1.0 / float(gp.sigma) ** 2, x_t_domain, x_t_boundary, gp.nugget, self.comm, compat_idx=compat_idx,
-                               round_diag=True, f16_graph=graph, f16_extra=getattr(gp, "_f16_extra", 0)).build(reuse=panel).factor()
+            ch2 = DistCholesky(d, gp.a, x_t_domain, x_t_boundary, gp.nugget, self.comm, compat_idx=compat_idx, round_diag=True,
+                               gram_bits=gram_bits).build(reuse=panel).factor()
             del panel
             rv = ch2.solve(b)
             self.chol = ch2

@@ -47,6 +47,13 @@ def _round_up(v, m):
     return (v + m - 1) // m * m
 
 
+def _f16_exact(*xs):
+    """Whether every entry of every array (torch tensors, NumPy arrays) is a float16 value, in the array's own dtype."""
+    import torch
+    ts = (x if isinstance(x, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(x)) for x in xs)
+    return all(bool((t.half().to(t.dtype) == t).all()) for t in ts)
+
+
 class GP(object):
     '''Gaussian Kernel Solver for high dimensional PDE'''
 
@@ -72,7 +79,7 @@ class GP(object):
         # one rounding per entry.  Brings the GP's relative L2 on the reference's experiments from <= 1e-4 to ~1e-5 of the logged numbers.  The
         # solvers' hot evaluation (float32 tree points) is unaffected.
         self.f16_graph = bool(f16_graph) and compat == "reference"
-        self._f16_extra = 8 if os.environ.get("SCASML_GP_F16_LEVEL") == "3" else 0     # exploratory: + the Hutchinson lap blocks (round16 bit 3)
+        self._f16_extra = _lib.ROUND16_F16_LAP if os.environ.get("SCASML_GP_F16_LEVEL") == "3" else 0     # exploratory
         self.laplacian_idx = None
         if compat == "reference":
             if isinstance(laplacian_idx, str):                   # the reference's own draw, models/GP.py:35
@@ -100,10 +107,10 @@ class GP(object):
         # compat="reference" evaluation kernel: "mfma" (matrix cores; needs float16-exact collocation points, else float64 is
         # used) or "float64" (one wavefront per point, rounding decided exactly as the NumPy statement decides it)
         self.compat_eval = os.environ.get("SCASML_GP_COMPAT_EVAL", "mfma")
-        # round16 argument of the compat evaluation: bit 0 = every kernel entry rounded to float16 (:43, 55-179), bit 1 = u_hat and eps_PDE
-        # leave as float16 values (:671, 769), bit 2 = one float16 plane of the evaluation point in x.y (matrix-core kernel, with bit 0 off).
-        # 3 is the reference's code; 6 is compat="reference-geometry"
-        self.eval_round16 = int(os.environ.get("SCASML_GP_EVAL_ROUND16", "6" if self.eval_geometry else "3"))
+        # round16 argument of the compat evaluation (_lib.ROUND16_*): entries rounded (:43, 55-179) and outputs rounded (:671, 769) are the
+        # reference's code (3); compat="reference-geometry" drops the entry rounding for one float16 plane of the evaluation point (6)
+        self.eval_round16 = int(os.environ.get("SCASML_GP_EVAL_ROUND16", _lib.ROUND16_OUTPUTS | (
+            _lib.ROUND16_ONE_PLANE if self.eval_geometry else _lib.ROUND16_ENTRIES)))
         self.profile = False            # bench.py: HIP-event time of every training stage into self.stage_ms
         self.stage_ms = {}
 
@@ -144,13 +151,37 @@ class GP(object):
         pts[:, :self.d + 1] = xt
         return pts, was_numpy, bound, bool(f16_rows)
 
-    def _split_for(self, x_bound):
-        """eval_split, demoted from the fp16 x 2 mode to the fp32-exact bf16 x 3 mode where the coordinates may leave the fp16
-        planes' range: 0.72 a |x|^2 with |x_k| <= x_bound must stay below 3e4 (include/scasml_hip.h, scasml_gp_model.x_bound)."""
-        split = int(self.eval_split)
-        if split == 22 and 0.7213 * (1.0 / float(self.sigma) ** 2) * x_bound * x_bound * (self.d + 1) > 3.0e4:
-            return 3
-        return split
+    @property
+    def a(self):
+        """The kernel's scale a = 1 / sigma^2 (models/GP.py:25, 41-43)."""
+        return 1.0 / float(self.sigma) ** 2
+
+    def _fp16_in_range(self, x_bound):
+        """The fp16 planes' range rule: 0.72 a |x|^2 with |x_k| <= x_bound (0 = the default 2) stays below 3e4 (scasml_gp_model.x_bound)."""
+        xb = x_bound if x_bound > 0 else 2.0
+        return 0.7213 * self.a * xb * xb * (self.d + 1) <= 3.0e4
+
+    def _f16_graph_rows(self, f16_rows):
+        """f16_graph applies: float16 rows against float16 collocation points of the as-coded fit."""
+        return self.f16_graph and f16_rows and getattr(self, "_colloc_is_f16", False)
+
+    def _fp16_planes(self, f16_rows=False):
+        """Whether the kernel _eval_rows chooses may carry the rows in fp16 planes, i.e. needs their coordinate bound."""
+        if self.compat is None:
+            return int(self.eval_split) == 22
+        return self.compat_eval == "mfma" and not self._f16_graph_rows(f16_rows)
+
+    def _gram_bits(self, x_dom, x_bdy, f16_rows=True):
+        """round16 of the as-coded Gram, Gram rows and cross rows: entries rounded; f16_graph on float16 rows and collocation points: float16 ops."""
+        graph = self.f16_graph and f16_rows and _f16_exact(x_dom, x_bdy)
+        return _lib.ROUND16_ENTRIES | (_lib.ROUND16_F16_OPS | self._f16_extra if graph else 0)
+
+    def _f64_model(self):
+        """The fit as the as-coded float64 kernels take it: collocation columns, n_dom, n_bdy, ldc, right_vector, Hutchinson indices."""
+        if self.right_vector is None:
+            raise _lib.ScasmlError("GP is not trained: call GPsolver(x_domain, x_boundary) first")
+        return (_lib.ptr(self._colloc_t), self.N_domain, self.N_boundary, self.N_domain + self.N_boundary, _lib.ptr(self._rv_dev),
+                self.laplacian_idx.ctypes.data_as(C.c_void_p))
 
     def _device_model(self, x_bound=0.0):
         if self.right_vector is None:
@@ -159,8 +190,9 @@ class GP(object):
         m.x_bound = float(x_bound)
         m.d, m.n_dom, m.n_bdy, m.n_pad = self.d, self.N_domain, self.N_boundary, self._n_pad
         m.kp = self._colloc.shape[1]
-        m.split = self._split_for(x_bound) if x_bound > 0 else int(self.eval_split)
-        m.a = 1.0 / float(self.sigma) ** 2
+        # a stated bound out of range demotes the fp16 x 2 split to bf16 x 3; without one (0) the library refuses what 2 would break
+        m.split = 3 if int(self.eval_split) == 22 and x_bound > 0 and not self._fp16_in_range(x_bound) else int(self.eval_split)
+        m.a = self.a
         m.sigma_eq = float(self.equation.sigma())
         m.mu_eq = float(self.equation.mu())
         m.eq_id = int(self.equation.eq_id)
@@ -174,56 +206,42 @@ class GP(object):
         tensors) lets far-out rows fall back to the bf16 x 3 arithmetic instead of overflowing the fp16 planes."""
         torch = _lib.require_gpu()
         out = torch.empty((pts.shape[0], 4), dtype=torch.float32, device="cuda")
-        fp16_planes = (int(self.eval_split) == 22 and self.compat is None) or (self.compat == "reference" and self.compat_eval == "mfma")
-        hb = host_bound
-        if self.compat == "reference" and self.f16_graph and f16_rows and getattr(self, "_colloc_is_f16", False):
-            # float16 rows against float16 collocation points: the float64 kernel with the reference's float16 op sequence for the Laplacian-free entries
-            N = self.N_domain + self.N_boundary
-            _lib.check(_lib.load().scasml_gp_eval_compat(self.d, 1.0 / float(self.sigma) ** 2, float(self.equation.sigma()), float(self.equation.mu()),
-                                                         int(self.equation.eq_id), _lib.ptr(self._colloc_t), self.N_domain, self.N_boundary, N,
-                                                         _lib.ptr(self._rv_dev), self.laplacian_idx.ctypes.data_as(C.c_void_p), (int(self.eval_round16) & 3) | 4 | self._f16_extra,
-                                                         _lib.ptr(pts), pts.shape[0], pts.shape[1], _lib.ptr(out), None, _lib.stream_ptr()), "gp_eval_compat")
-            return out
-        xb = (hb if hb is not None else float(pts.abs().max())) if pts.shape[0] and fp16_planes else 0.0
-        self._eval_rows(pts, pts.shape[0], 0, None, out, x_bound=max(xb, 2.0) if xb > 0 else 0.0)
+        xb = (host_bound if host_bound is not None else float(pts.abs().max())) if pts.shape[0] and self._fp16_planes(f16_rows) else 0.0
+        self._eval_rows(pts, pts.shape[0], 0, None, out, x_bound=max(xb, 2.0) if xb > 0 else 0.0, f16_rows=f16_rows)
         return out
 
-    def _eval_rows(self, pts, n_rows, rows_per_site, kinds, out4, x_bound=0.0, order=None):
+    def _eval_rows(self, pts, n_rows, rows_per_site, kinds, out4, x_bound=0.0, order=None, f16_rows=False):
         """(u_hat, div u_hat, eps_PDE, dt u_hat) of the first n_rows point rows into out4: the one place the solvers and
-        predict / compute_PDE_loss reach the evaluation kernels (kinds: per-site byte of scasml_plan_site_kinds or None; order: device int32
-        list of the sites to evaluate, in launch order -- the as-coded matrix-core kernel then launches over those sites only)."""
+        predict / compute_PDE_loss reach the evaluation kernels, and where the kernel is chosen (kinds: per-site byte of scasml_plan_site_kinds
+        or None; order: device int32 list of the sites to evaluate, in launch order -- the as-coded matrix-core kernel then launches over those
+        sites only; f16_rows: the caller's rows were float16).  As coded: the matrix-core kernel where the rows may take fp16 planes
+        (_fp16_planes) within their range, else the float64 kernel; the documented operators: the split demoted out of that range."""
         lib = _lib.load()
         if self.right_vector is None:
             raise _lib.ScasmlError("GP is not trained: call GPsolver(x_domain, x_boundary) first")
-        if self.compat == "reference":
-            a = 1.0 / float(self.sigma) ** 2
-            xb = x_bound if x_bound > 0 else 2.0
-            if self.compat_eval == "mfma" and self._compat_model is not None and 0.7213 * a * xb * xb * (self.d + 1) <= 3.0e4:
-                if order is not None and kinds is not None and rows_per_site % 32 == 0 and n_rows % rows_per_site == 0:
-                    _lib.check(lib.scasml_gp_eval_compat_site_list(
-                        self.d, a, float(self.equation.sigma()), float(self.equation.mu()), int(self.equation.eq_id), _lib.ptr(self._compat_model),
-                        self.N_domain, self.N_boundary, self.laplacian_idx.ctypes.data_as(C.c_void_p), int(self.eval_round16), float(x_bound), _lib.ptr(pts),
-                        n_rows, rows_per_site, _lib.ptr(kinds), _lib.ptr(order), int(order.numel()), _lib.ptr(out4), None, _lib.stream_ptr()),
-                        "gp_eval_compat_site_list")
-                    return
-                _lib.check(lib.scasml_gp_eval_compat_sites(
-                    self.d, a, float(self.equation.sigma()), float(self.equation.mu()), int(self.equation.eq_id), _lib.ptr(self._compat_model),
-                    self.N_domain, self.N_boundary, self.laplacian_idx.ctypes.data_as(C.c_void_p), int(self.eval_round16), float(x_bound), _lib.ptr(pts), n_rows,
-                    rows_per_site if kinds is not None else 0, _lib.ptr(kinds) if kinds is not None else None, _lib.ptr(out4), None,
-                    _lib.stream_ptr()), "gp_eval_compat_sites")
-                return
-            N = self.N_domain + self.N_boundary
-            _lib.check(lib.scasml_gp_eval_compat(self.d, a, float(self.equation.sigma()),
-                                                 float(self.equation.mu()), int(self.equation.eq_id), _lib.ptr(self._colloc_t), self.N_domain, self.N_boundary, N, _lib.ptr(self._rv_dev),
-                                                 self.laplacian_idx.ctypes.data_as(C.c_void_p), int(self.eval_round16) & 3, _lib.ptr(pts), n_rows,
-                                                 pts.shape[1], _lib.ptr(out4), None, _lib.stream_ptr()), "gp_eval_compat")
+        if self.compat is None:
+            model = self._device_model(x_bound)
+            if kinds is None:
+                _lib.check(lib.scasml_gp_eval(C.byref(model), _lib.ptr(pts), n_rows, _lib.ptr(out4), None, _lib.stream_ptr()), "gp_eval")
+            else:
+                _lib.check(lib.scasml_gp_eval_sites(C.byref(model), _lib.ptr(pts), n_rows, rows_per_site, _lib.ptr(kinds),
+                                                    _lib.ptr(out4), _lib.stream_ptr()), "gp_eval")
             return
-        model = self._device_model(x_bound)
-        if kinds is None:
-            _lib.check(lib.scasml_gp_eval(C.byref(model), _lib.ptr(pts), n_rows, _lib.ptr(out4), None, _lib.stream_ptr()), "gp_eval")
-        else:
-            _lib.check(lib.scasml_gp_eval_sites(C.byref(model), _lib.ptr(pts), n_rows, rows_per_site, _lib.ptr(kinds),
-                                                _lib.ptr(out4), _lib.stream_ptr()), "gp_eval")
+        r16 = int(self.eval_round16)
+        if self._fp16_planes(f16_rows) and self._compat_model is not None and self._fp16_in_range(x_bound):
+            args = (_lib.ptr(self._compat_model), self.N_domain, self.N_boundary, self.laplacian_idx.ctypes.data_as(C.c_void_p), r16, float(x_bound),
+                    _lib.ptr(pts), n_rows)
+            if order is not None and kinds is not None and rows_per_site % 32 == 0 and n_rows % rows_per_site == 0:
+                name, args = "gp_eval_compat_site_list", args + (rows_per_site, _lib.ptr(kinds), _lib.ptr(order), int(order.numel()))
+            else:
+                name, args = "gp_eval_compat_sites", args + (rows_per_site if kinds is not None else 0, _lib.ptr(kinds))
+        else:                 # the float64 kernel: no one-plane mode; the reference's float16 op sequence on f16_graph rows
+            r16 &= _lib.ROUND16_ENTRIES | _lib.ROUND16_OUTPUTS
+            if self._f16_graph_rows(f16_rows):
+                r16 |= _lib.ROUND16_F16_OPS | self._f16_extra
+            name, args = "gp_eval_compat", self._f64_model() + (r16, _lib.ptr(pts), n_rows, pts.shape[1])
+        head = (self.d, self.a, float(self.equation.sigma()), float(self.equation.mu()), int(self.equation.eq_id))
+        _lib.check(getattr(lib, "scasml_" + name)(*head, *args, _lib.ptr(out4), None, _lib.stream_ptr()), name)
 
     def _predict_device(self, x_dev):
         pts, _, hb, f16 = self._points_device(x_dev)
@@ -242,15 +260,11 @@ class GP(object):
         self._xd, self._xb = xd, xb
         s = _lib.stream_ptr()
         K = torch.empty((M, M), dtype=torch.float64, device="cuda")
-        if self.compat == "reference":
-            colloc_f16 = bool((xd.half().float() == xd).all()) and bool((xb.half().float() == xb).all())
-            gram_bits = 1 | ((4 | self._f16_extra) if (self.f16_graph and colloc_f16) else 0)
-            self._stage("gram", lambda: _lib.check(lib.scasml_gp_gram_compat(
-                self.d, 1.0 / float(self.sigma) ** 2, _lib.ptr(xd), self.N_domain, _lib.ptr(xb), self.N_boundary,
-                self.laplacian_idx.ctypes.data_as(C.c_void_p), gram_bits, _lib.ptr(K), s), "gp_gram_compat"))
-        else:
-            self._stage("gram", lambda: _lib.check(lib.scasml_gp_gram(
-                self.d, 1.0 / float(self.sigma) ** 2, _lib.ptr(xd), self.N_domain, _lib.ptr(xb), self.N_boundary, _lib.ptr(K), s), "gp_gram"))
+        as_coded = self.compat == "reference"
+        name = "gp_gram_compat" if as_coded else "gp_gram"
+        compat_args = (self.laplacian_idx.ctypes.data_as(C.c_void_p), self._gram_bits(xd, xb)) if as_coded else ()
+        self._stage("gram", lambda: _lib.check(getattr(lib, "scasml_" + name)(
+            self.d, self.a, _lib.ptr(xd), self.N_domain, _lib.ptr(xb), self.N_boundary, *compat_args, _lib.ptr(K), s), name))
         Mp = _round_up(M, 32)
         L = torch.eye(Mp, dtype=torch.float64, device="cuda")
         L[:M, :M] = K
@@ -260,7 +274,7 @@ class GP(object):
             raise ValueError("Cholesky decomposition resulted in NaN values.")        # models/GP.py:264-265
         self._L_pad = L
         self.cholesky_phi_phi_perturb = L[:M, :M]
-        if self.compat == "reference":     # kernel_phi_phi_perturb.astype(float16) (:268): the entries are float16 already, the diagonal moves
+        if as_coded:                       # kernel_phi_phi_perturb.astype(float16) (:268): the entries are float16 already, the diagonal moves
             _lib.check(lib.scasml_round16_diag(_lib.ptr(K), M, M, float(self.nugget), s), "round16_diag")
         else:
             K.diagonal().add_(self.nugget)
@@ -271,7 +285,7 @@ class GP(object):
 
     def bdy_g(self, x_t_boundary):
         xb = np.asarray(x_t_boundary)
-        if self.compat == "reference" and np.array_equal(xb.astype(np.float16).astype(xb.dtype), xb):
+        if self.compat == "reference" and _f16_exact(xb):
             xb = xb.astype(np.float16)      # the reference's boundary points are float16 arrays: g is then its float16 graph (equations.py:259-261)
         else:
             xb = xb.astype(np.float64)      # the documented operators: no float16 emulation anywhere
@@ -420,35 +434,32 @@ class GP(object):
     def _pack(self, rv):
         torch = _lib.require_gpu()
         lib = _lib.load()
+        N = self.N_domain + self.N_boundary
+        self._n_pad = _round_up(N, _lib.GP_TILE)
+        # collocation points that are exactly float16 (the reference's deepxde float16 arrays are) need one plane, and are what the
+        # matrix-core form of the as-coded surrogate needs
+        self._colloc_is_f16 = _f16_exact(self._xd, self._xb)
         if self.compat == "reference":
-            N = self.N_domain + self.N_boundary
             self._colloc_t = torch.empty((self.d + 1, N), dtype=torch.float64, device="cuda")
             _lib.check(lib.scasml_gp_compat_pack(self.d, _lib.ptr(self._xd), self.N_domain, _lib.ptr(self._xb), self.N_boundary,
                                                  _lib.ptr(self._colloc_t), N, _lib.stream_ptr()), "gp_compat_pack")
             self._rv_dev = rv.to(dtype=torch.float64).contiguous().clone()
-            # matrix-core form of the same surrogate: needs every collocation coordinate to be exactly float16
-            self._colloc_is_f16 = bool((self._xd.half().float() == self._xd).all()) and bool((self._xb.half().float() == self._xb).all())
             self._compat_model = None
             if self._colloc_is_f16:
-                n_pad = _round_up(N, _lib.GP_TILE)
-                self._compat_model = torch.empty((int(lib.scasml_gp_compat_model_floats(self.d, n_pad)),), dtype=torch.float32, device="cuda")
-                _lib.check(lib.scasml_gp_compat_pack_mfma(self.d, 1.0 / float(self.sigma) ** 2, _lib.ptr(self._xd), self.N_domain, _lib.ptr(self._xb),
+                self._compat_model = torch.empty((int(lib.scasml_gp_compat_model_floats(self.d, self._n_pad)),), dtype=torch.float32, device="cuda")
+                _lib.check(lib.scasml_gp_compat_pack_mfma(self.d, self.a, _lib.ptr(self._xd), self.N_domain, _lib.ptr(self._xb),
                                                           self.N_boundary, _lib.ptr(self._rv_dev), self.laplacian_idx.ctypes.data_as(C.c_void_p),
                                                           _lib.ptr(self._compat_model), _lib.stream_ptr()), "gp_compat_pack_mfma")
-            torch.cuda.current_stream().synchronize()
-            return
-        kp = int(lib.scasml_point_stride(self.d))
-        self._n_pad = _round_up(self.N_domain + self.N_boundary, _lib.GP_TILE)
-        self._colloc = torch.empty((self._n_pad, kp), dtype=torch.float32, device="cuda")
-        self._frag = torch.empty((self._n_pad * kp,), dtype=torch.float32, device="cuda")
-        self._bf16 = torch.empty((int(lib.scasml_gp_plane_halfwords(self.d, self._n_pad)),), dtype=torch.int16, device="cuda")
-        self._coef = torch.empty((int(lib.scasml_gp_coef_floats(self._n_pad)),), dtype=torch.float32, device="cuda")
-        rv = rv.contiguous()
-        # collocation points that are exactly fp16 (the reference's deepxde float16 arrays are) need one plane
-        self._colloc_is_f16 = bool((self._xd.half().float() == self._xd).all()) and bool((self._xb.half().float() == self._xb).all())
-        _lib.check(lib.scasml_gp_pack(self.d, 1.0 / float(self.sigma) ** 2, float(self.T), _lib.ptr(self._xd), self.N_domain,
-                                      _lib.ptr(self._xb), self.N_boundary, _lib.ptr(rv), _lib.ptr(self._colloc),
-                                      _lib.ptr(self._frag), _lib.ptr(self._bf16), _lib.ptr(self._coef), _lib.stream_ptr()), "gp_pack")
+        else:
+            kp = int(lib.scasml_point_stride(self.d))
+            self._colloc = torch.empty((self._n_pad, kp), dtype=torch.float32, device="cuda")
+            self._frag = torch.empty((self._n_pad * kp,), dtype=torch.float32, device="cuda")
+            self._bf16 = torch.empty((int(lib.scasml_gp_plane_halfwords(self.d, self._n_pad)),), dtype=torch.int16, device="cuda")
+            self._coef = torch.empty((int(lib.scasml_gp_coef_floats(self._n_pad)),), dtype=torch.float32, device="cuda")
+            rv = rv.contiguous()
+            _lib.check(lib.scasml_gp_pack(self.d, self.a, float(self.T), _lib.ptr(self._xd), self.N_domain,
+                                          _lib.ptr(self._xb), self.N_boundary, _lib.ptr(rv), _lib.ptr(self._colloc),
+                                          _lib.ptr(self._frag), _lib.ptr(self._bf16), _lib.ptr(self._coef), _lib.stream_ptr()), "gp_pack")
         torch.cuda.current_stream().synchronize()                  # rv may be freed by the caller
 
     def load_right_vector(self, x_t_domain, x_t_boundary, right_vector):
@@ -475,7 +486,7 @@ class GP(object):
                 "loss_history": np.asarray(getattr(self, "loss_history", []), dtype=np.float64),
                 "nugget": np.float64(self.nugget), "T": np.float64(self.T), "compat": np.str_(self.compat or ""), "f16_graph": np.bool_(self.f16_graph),
                 # the float16 op sequence is only taken on float16 collocation points; otherwise the fit silently used one rounding per entry
-                "f16_graph_effective": np.bool_(self.f16_graph and bool(getattr(self, "_colloc_is_f16", False))),
+                "f16_graph_effective": np.bool_(self._f16_graph_rows(True)),
                 "laplacian_idx": np.asarray(self.laplacian_idx if self.laplacian_idx is not None else [], dtype=np.int32)}
 
     def load_state_dict(self, state):
@@ -516,16 +527,12 @@ class GP(object):
         lib = _lib.load()
         pts, was_numpy, _, _ = self._points_device(x_t_infer)
         grad = torch.empty((pts.shape[0], self.d + 1), dtype=torch.float32, device="cuda")
-        if self.compat == "reference":      # autodiff of the as-coded u_hat (through the float16 casts), result cast to float16 (:687)
-            if self.right_vector is None:
-                raise _lib.ScasmlError("GP is not trained: call GPsolver(x_domain, x_boundary) first")
-            N = self.N_domain + self.N_boundary
-            _lib.check(lib.scasml_gp_gradient_compat(self.d, 1.0 / float(self.sigma) ** 2, _lib.ptr(self._colloc_t), self.N_domain, self.N_boundary, N,
-                                                     _lib.ptr(self._rv_dev), self.laplacian_idx.ctypes.data_as(C.c_void_p), 1, _lib.ptr(pts),
-                                                     pts.shape[0], pts.shape[1], _lib.ptr(grad), _lib.stream_ptr()), "gp_gradient_compat")
-            return grad.cpu().numpy() if was_numpy else grad
-        model = self._device_model()
-        _lib.check(lib.scasml_gp_gradient(C.byref(model), _lib.ptr(pts), pts.shape[0], _lib.ptr(grad), _lib.stream_ptr()), "gp_gradient")
+        if self.compat is None:
+            model = self._device_model()
+            _lib.check(lib.scasml_gp_gradient(C.byref(model), _lib.ptr(pts), pts.shape[0], _lib.ptr(grad), _lib.stream_ptr()), "gp_gradient")
+        else:      # autodiff of the as-coded u_hat (through the float16 casts); any nonzero round16 casts the result to float16 (:687)
+            _lib.check(lib.scasml_gp_gradient_compat(self.d, self.a, *self._f64_model(), _lib.ROUND16_ENTRIES, _lib.ptr(pts), pts.shape[0],
+                                                     pts.shape[1], _lib.ptr(grad), _lib.stream_ptr()), "gp_gradient_compat")
         return grad.cpu().numpy() if was_numpy else grad
 
     def compute_PDE_loss(self, x_t_infer):
@@ -555,18 +562,14 @@ class GP(object):
             raise ValueError("the cross-kernel builders need at least one domain point")
         M = 4 * nd + nb
         as_coded = self.compat == "reference"
-        r16 = 1 if as_coded else 0
-        if as_coded and self.f16_graph and f16_rows:
-            colloc = torch.cat([xd, xb])
-            if bool((colloc.half().float() == colloc).all()):          # float16 rows on float16 collocation points: the reference's float16 op sequence
-                r16 |= 4 | self._f16_extra
+        r16 = self._gram_bits(xd, xb, f16_rows) if as_coded else 0
         shape = (ni, M, self.d + 1) if op == 4 else (ni, M)
         out = torch.empty(shape, dtype=torch.float64, device="cuda")
         if ni:
             rows_per_call = 65535 * 16
             for lo in range(0, ni, rows_per_call):
                 n = min(rows_per_call, ni - lo)
-                _lib.check(lib.scasml_gp_cross_rows(self.d, 1.0 / float(self.sigma) ** 2, _lib.ptr(xd), nd, _lib.ptr(xb) if nb else None, nb,
+                _lib.check(lib.scasml_gp_cross_rows(self.d, self.a, _lib.ptr(xd), nd, _lib.ptr(xb) if nb else None, nb,
                                                     self.laplacian_idx.ctypes.data_as(C.c_void_p) if as_coded else None, r16, 0 if as_coded else 1, op,
                                                     _lib.ptr(xi[lo:]), n, self.d + 1, _lib.ptr(out[lo:]), M, _lib.stream_ptr()), "gp_cross_rows")
         if as_coded:

@@ -83,13 +83,13 @@ def assert_explained(eng, n, par, x_rows, root0, stream_id, want, report=None):
     seen = {}
 
     def capture(tag):
-        def f(pts, n_rows, rows_per_site, kinds, out4, x_bound=0.0, order=None):
-            method(gp, pts, n_rows, rows_per_site, kinds, out4, x_bound=x_bound, order=order)
+        def f(pts, n_rows, rows_per_site, kinds, out4, x_bound=0.0, order=None, f16_rows=False):
+            method(gp, pts, n_rows, rows_per_site, kinds, out4, x_bound=x_bound, order=order, f16_rows=f16_rows)
             seen[tag] = (out4[:n_rows].clone(), int(rows_per_site), kinds.clone())
         return f
 
     def inject(vals):
-        def f(pts, n_rows, rows_per_site, kinds, out4, x_bound=0.0, order=None):
+        def f(pts, n_rows, rows_per_site, kinds, out4, x_bound=0.0, order=None, f16_rows=False):
             out4[:n_rows].copy_(vals)
         return f
 
