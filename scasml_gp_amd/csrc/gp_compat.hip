@@ -27,16 +27,15 @@ __device__ __forceinline__ double round16(double v, int on) {
     if (!on) return v;
     const double av = fabs(v);
     if (!(av == av)) return v;
-    if (av >= 65520.0) return v < 0 ? -INFINITY : INFINITY;
-    if (av < 5.9604644775390625e-8 * 0.5) return v < 0 ? -0.0 : 0.0;     // below half the smallest subnormal
+    if (av >= 65520.0) return copysign(INFINITY, v);
+    if (av < 5.9604644775390625e-8 * 0.5) return copysign(0.0, v);      // below half the smallest subnormal; -0 stays -0
     int e;
     frexp(av, &e);                                     // av = m 2^e, m in [0.5, 1)
     int ulp_exp = e - 11;                              // 11 significant bits
     if (ulp_exp < -24) ulp_exp = -24;                  // subnormal spacing 2^-24
     const double q = ldexp(av, -ulp_exp);              // integer part carries the kept bits
     const double r = rint(q);                          // RNE (default rounding mode)
-    const double o = ldexp(r, ulp_exp);
-    return v < 0 ? -o : o;
+    return copysign(ldexp(r, ulp_exp), v);
 }
 
 // The three geometries of one (x, y) pair.  x, y: pointers to d+1 coordinates with strides sx, sy (elements).

@@ -50,7 +50,17 @@ def main():
                         dt=dt, div=div, lap=lap, pde=gp.compute_PDE_loss(X), x_t=xt,
                         scasml_quad_2_2=PicardOracle(eq, "quad", gp=gp, seed=3, stream=0).uz_solve(2, 2, xt),
                         scasml_fh_2_3=PicardOracle(eq, "fh", gp=gp, seed=3, stream=0).uz_solve(2, 3, xt))
+    quad_level5()
     print("wrote", sorted(f for f in os.listdir(HERE) if f.endswith(".npz")))
+
+
+def quad_level5():
+    """4. quadrature n = rho = 5 on one root at d = 13 (113 745 tree sites, a minute or more of oracle time): the target of
+    tests/test_gpu_picard_sweep.py, whose other levels it computes live.  Seed and stream as that file's _Tree."""
+    d = 13
+    xt = np.concatenate(sample_points(np.random.default_rng(7), d, 3, 1))[1:2]
+    uz = PicardOracle(GradDependentNonlinear(d + 1), "quad", seed=7, stream=3).uz_solve(5, 5, xt)
+    np.savez_compressed(os.path.join(HERE, "oracle_quad5_d13.npz"), x_t=xt, uz=uz)
 
 
 if __name__ == "__main__":
