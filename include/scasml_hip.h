@@ -449,6 +449,16 @@ int scasml_gp_cross_rows(int32_t d, double a, const float *x_dom, int32_t n_dom,
                          int32_t round16, int32_t surrogate, int32_t op, const float *x_inf, int64_t n_inf, int64_t ld_inf, double *out,
                          int64_t ld, void *stream);
 
+/* Added within ABI 7 (additive: no existing entry point or struct changes).  Posterior variance of the surrogate at n points, float64:
+ *   var_out[i] = prior - | L^-1 k(x_i) |^2
+ * from the lower Cholesky factor L of K(phi, phi) + nugget I (Mp x Mp row-major, Mp a multiple of 32: the factor identity-padded as scasml_cholesky
+ * leaves it) and the op-0 feature rows of scasml_gp_cross_rows: `rows` is n x ld row-major, row i in rows[i*ld .. i*ld + Mp) with columns M .. Mp zero.
+ * `rows` is OVERWRITTEN with rows L^-T (row i becomes (L^-1 k(x_i))^T); prior = kappa(x, x) = 1 for this library's kernels.  One launch: a workgroup
+ * owns 64 point rows and sweeps the block columns of L by itself (v_mfma_f64_16x16x4_f64 updates, the small triangular solves in LDS, the sums of
+ * squares in registers; csrc/gp_variance.hip) -- no atomics, and a row's result is a function of that row, L and Mp alone, bit for bit: it does not
+ * depend on n, on the row's position or on the other rows.  n = 0 does nothing. */
+int scasml_gp_variance(const double *L, int64_t Mp, double *rows, int64_t ld, int64_t n, double prior, double *var_out, void *stream);
+
 /* ------------------------------------------------------------------ block-row distributed Gram / Cholesky / solves
  * For collocation sets whose K(phi, phi) does not fit one GPU (BASELINE configs[4]: 1e5 points, M = 350 000, 980 GB float64)
  * the matrix is cut into block rows of SCASML_DIST_BLOCK feature rows, block row i owned by rank i % world and stored as a

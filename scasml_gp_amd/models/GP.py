@@ -273,6 +273,7 @@ class GP(object):
         if int(info.item()) != 0 or bool(torch.isnan(L).any()):
             raise ValueError("Cholesky decomposition resulted in NaN values.")        # models/GP.py:264-265
         self._L_pad = L
+        self._L_made_for = (xd, xb, self.nugget)           # predict_variance: the factor belongs to these collocation tensors
         self.cholesky_phi_phi_perturb = L[:M, :M]
         if as_coded:                       # kernel_phi_phi_perturb.astype(float16) (:268): the entries are float16 already, the diagonal moves
             _lib.check(lib.scasml_round16_diag(_lib.ptr(K), M, M, float(self.nugget), s), "round16_diag")
@@ -520,6 +521,65 @@ class GP(object):
         pts, was_numpy, hb, f16 = self._points_device(x_t_infer)
         out = self._eval_device(pts, hb, f16)[:, 0:1]
         return out.cpu().numpy() if was_numpy else out
+
+    # posterior variance (no counterpart in models/GP.py, which keeps only right_vector): var(x) = kappa(x, x) - |L^-1 K(x, phi)|^2 with the factor
+    # L of K(phi, phi) + nugget I that kernel_phi_phi leaves on the device
+    variance_buffer_bytes = 1 << 30     # cap of the (points x Mp) float64 row buffer predict_variance works in; n is walked in chunks under it
+
+    def _variance_factor(self):
+        """The padded float64 factor of K(phi, phi) + nugget I for the collocation points this GP holds.  kernel_phi_phi / GPsolver leave it;
+        after load_state_dict / load / load_right_vector it is rebuilt here, once, by kernel_phi_phi's own device work (Gram + Cholesky, same nugget)."""
+        if getattr(self, "_xd", None) is None:
+            raise _lib.ScasmlError("no collocation points yet: call GPsolver / kernel_phi_phi / load_right_vector first")
+        made_for = getattr(self, "_L_made_for", None)
+        if getattr(self, "_L_pad", None) is None or made_for is None or made_for[0] is not self._xd or made_for[1] is not self._xb or made_for[2] != self.nugget:
+            self.kernel_phi_phi(self.x_t_domain, self.x_t_boundary)
+        return self._L_pad
+
+    def predict_variance(self, x_t_infer):
+        '''(n, 1) float64 posterior variance  var(x) = kappa(x, x) - |L^-1 K(x, phi)|^2,  kappa(x, x) = 1  (NumPy in, NumPy out; CUDA tensor in, CUDA
+        tensor out; the raw value, not clamped).
+
+        compat=None: the posterior variance of u(x) under the prior kappa given noisy observations (noise variance = nugget) of the collocation
+        functionals [u(dom), u(bdy), Lap(dom), dt(dom), div(dom)]; it lies in [0, 1] up to rounding.  compat="reference": the as-coded ANALOGUE --
+        the same formula on the matrices the reference's code builds (float16-valued entries, 5-index Hutchinson Laplacian blocks on the shifted
+        argument, lower triangle of K); those are not the Gram matrix and cross-covariances of one kernel, so the value carries no sign guarantee.
+        It depends on the collocation points, sigma and nugget only -- not on the fit: kernel_phi_phi(x_dom, x_bdy) is enough, also for equations
+        GPsolver has no Newton kernels for.
+
+        The feature rows (scasml_gp_cross_rows, op 0) are written straight into a padded (points x Mp) float64 buffer and solved in place by
+        scasml_gp_variance (one FP64-MFMA launch per chunk, the sums of squares in the same kernel); n is walked in chunks that keep the buffer
+        under ``variance_buffer_bytes``.  Every point's value is a function of that point alone, bit for bit: chunking and order do not change it.
+        Needs the factor of K(phi, phi) + nugget I: GPsolver / kernel_phi_phi leave it; after load_state_dict / load / load_right_vector the first
+        call rebuilds it (one Gram + one Cholesky factorisation) and keeps it.  state_dict does not carry it.'''
+        torch = _lib.require_gpu()
+        lib = _lib.load()
+        L = self._variance_factor()
+        was_numpy = not isinstance(x_t_infer, torch.Tensor)
+        f16_rows = (np.asarray(x_t_infer).dtype == np.float16) if was_numpy else x_t_infer.dtype == torch.float16
+        xi = x_t_infer if not was_numpy else torch.from_numpy(np.ascontiguousarray(np.asarray(x_t_infer), dtype=np.float32))
+        xi = xi.to(device="cuda", dtype=torch.float32).contiguous()
+        if xi.dim() != 2 or xi.shape[1] != self.d + 1:
+            raise ValueError("points must have shape (n, %d), got %s" % (self.d + 1, tuple(xi.shape)))
+        n, Mp = xi.shape[0], L.shape[0]
+        as_coded = self.compat == "reference"
+        r16 = self._gram_bits(self._xd, self._xb, f16_rows) if as_coded else 0
+        var = torch.empty((n, 1), dtype=torch.float64, device="cuda")
+        chunk = int(max(1, min(self.variance_buffer_bytes // (8 * Mp), 65535 * 16, n)))
+        rows = torch.zeros((chunk, Mp), dtype=torch.float64, device="cuda") if n else None   # columns M .. Mp stay zero (L is identity there)
+        s = _lib.stream_ptr()
+        for lo in range(0, n, chunk):
+            m = min(chunk, n - lo)
+            _lib.check(lib.scasml_gp_cross_rows(self.d, self.a, _lib.ptr(self._xd), self.N_domain, _lib.ptr(self._xb) if self.N_boundary else None,
+                                                self.N_boundary, self.laplacian_idx.ctypes.data_as(C.c_void_p) if as_coded else None, r16,
+                                                0 if as_coded else 1, 0, _lib.ptr(xi[lo:]), m, self.d + 1, _lib.ptr(rows), Mp, s), "gp_cross_rows")
+            _lib.check(lib.scasml_gp_variance(_lib.ptr(L), Mp, _lib.ptr(rows), Mp, m, 1.0, _lib.ptr(var[lo:]), s), "gp_variance")
+        return var.cpu().numpy() if was_numpy else var
+
+    def predict_std(self, x_t_infer):
+        '''(n, 1) float64 posterior standard deviation sqrt(max(predict_variance, 0)).'''
+        var = self.predict_variance(x_t_infer)
+        return np.sqrt(np.maximum(var, 0.0)) if isinstance(var, np.ndarray) else var.clamp_min(0.0).sqrt()
 
     def compute_gradient(self, x_t_infer, sol_infer=None):
         '''(n, d+1) gradient of the posterior mean, time derivative last (models/GP.py:673-687).'''
