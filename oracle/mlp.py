@@ -122,10 +122,25 @@ class PicardOracle:
         self.sites_executed = 0
         jx = None
         if self.jax_stream:
-            jx = (self.jax_splits, np.arange(B, dtype=np.uint64))
+            # the root's row in the reference's flattened batch is root0 + local, in 64 bits (no 32-bit wrap: the row is not a Philox counter
+            # word), as in picard_tree_kernel and as PicardEngine.solve relies on when it cuts a batch into chunks with root0 + b0
+            jx = (self.jax_splits, np.uint64(int(root0)) + np.arange(B, dtype=np.uint64))
             if self.variant == "quad":               # the full-history solvers draw everything from the one terminal key
                 self.jax_splits += self._jax_splits_in_call(n)
         return self._uz(n, x_t[:, :-1].copy(), x_t[:, -1].copy(), roots, 0, top=True, cbase=0, jx=jx)
+
+    def uz_call(self, level, par, x_t, root0=0, base=0):
+        """(u, z) of ONE inner call of the recursion on the Philox stream: the level-``level`` call whose first RNG site is ``base``, started at
+        the rows ``x_t`` (the stored point of its parent node), clipped as every inner call is.  What a stage of the staged tree writes per
+        subtree (csrc/picard_staged.hip)."""
+        if self.jax_stream:
+            raise NotImplementedError("uz_call addresses a call by its Philox site; the reference's stream addresses it by key slot and batch row")
+        x_t = np.asarray(x_t, dtype=np.float32).astype(np.float64)
+        self.par = int(par)
+        self.tab = approx_parameters(self.par, self.T) if self.variant == "quad" else None
+        self._shard, self._owner = (0, 1), None
+        roots = np.arange(root0, root0 + x_t.shape[0], dtype=np.uint64)
+        return self._uz(int(level), x_t[:, :-1].copy(), x_t[:, -1].copy(), roots, int(base))
 
     # the reference's random stream ----------------------------------------------------------------
     def _jax_splits_in_call(self, n):

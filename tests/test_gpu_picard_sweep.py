@@ -165,14 +165,32 @@ class _Tree:
         self.eng = PicardEngine(self.eq, variant, gp=self.sur, seed=seed)
         self.prob = self.eng.problem()
         self.kp = _kp(d)
+        self._keys = {}
         assert self.prob.sigma == SIGMA and self.prob.clip == np.float32(0.1 if surrogate else 1.0)
 
     def plan(self, n, par):
         return self.eng.plan(n, par)
 
-    def rng(self, root0=0, rank=0, world=1, flags=0, owner=None):
+    def rng(self, root0=0, rank=0, world=1, flags=0, owner=None, jax=None):
+        """jax = (n, par): the reference's own stream (RNG_JAX_STREAM) for that plan, from the initial key state."""
         from scasml_gp_amd import _lib
-        return _lib.Rng(self.seed, self.stream, root0, rank, world, flags, 0, owner, None)
+        keys = None
+        if jax is not None:
+            flags |= _lib.RNG_JAX_STREAM
+            keys = self.jax_keys(*jax).data_ptr()
+        return _lib.Rng(self.seed, self.stream, root0, rank, world, flags, 0, owner, keys)
+
+    def jax_keys(self, n, par):
+        """Device key words [terminal key | path sub-keys] of a solve that starts at PRNGKey(0), as PicardEngine._jax_keys builds them; kept
+        alive here for as long as the launches that read them."""
+        import torch
+        from scasml_gp_amd import threefry
+        if (n, par) not in self._keys:
+            plan = self.plan(n, par)
+            q = [[int(plan.term[level][l].q) for l in range(level)] for level in range(plan.n + 1)]
+            words, _ = threefry.solver_key_words(q, plan.n, (0, 0), quadrature=self.variant == "quad")
+            self._keys[(n, par)] = torch.from_numpy(words.view(np.int32).reshape(-1).copy()).cuda()
+        return self._keys[(n, par)]
 
     def launch(self, mode, plan, x, B, stride, rng, pts=None, vals=None, out=None, uhat=None, prob=None):
         import torch
@@ -215,7 +233,7 @@ class _Tree:
 
     def oracle(self, n, par, xt, **kw):
         from oracle.mlp import PicardOracle
-        flags = {k: kw.pop(k) for k in ("compat_crn", "compat_f16") if k in kw}
+        flags = {k: kw.pop(k) for k in ("compat_crn", "compat_f16", "jax_stream") if k in kw}     # a fresh oracle: the initial key state
         return PicardOracle(self.oeq, self.variant, gp=self.sur, seed=self.seed, stream=self.stream, **flags).uz_solve(n, par, xt, **kw)
 
 

@@ -223,3 +223,36 @@ def test_scasml_oracle_on_the_reference_normals_lands_on_the_logged_numbers_at_d
     assert abs(rel - want) <= 5e-3 * want, (rel, want)
     lo, hi, mean, std = _numbers(_line(d, "ScaSML L1"))[:4]
     assert abs(float(err.mean()) - mean) <= 6e-3 * mean and abs(float(err.max()) - hi) <= 4 * 2.0 ** -11
+
+
+@pytest.mark.parametrize("variant,n,par", [("quad", 2, 2), ("quad", 3, 3), ("fh", 2, 3), ("fh", 3, 2)])
+def test_reference_stream_rows_start_at_root0(variant, n, par):
+    """A root's draws are addressed by its row in the reference's flattened batch, root0 + local in 64 bits (what picard_tree_kernel does
+    and PicardEngine.solve relies on when it cuts a batch into chunks with root0 + b0): uz_solve(xt[r:r+k], root0=r) is rows r..r+k of
+    uz_solve(xt), bit for bit -- also where (root0 + i) * width * d is past 2^32 -- and the key state advances as without root0."""
+    from oracle.equation import GradDependentNonlinear, sample_points
+    from oracle.mlp import PicardOracle
+    d, B = 7, 12
+    eq = GradDependentNonlinear(d + 1)
+    xt = np.concatenate(sample_points(np.random.default_rng(3), d, B - 3, 3)).astype(np.float32)
+    fresh = lambda: PicardOracle(eq, variant, jax_stream=True)
+    whole = fresh()
+    want = whole.uz_solve(n, par, xt)
+    assert np.isfinite(want).all()
+    for r, k in ((0, B), (1, 4), (5, 7), (11, 1)):
+        part = fresh()
+        assert np.array_equal(part.uz_solve(n, par, xt[r:r + k], root0=r), want[r:r + k]), (r, k)
+        assert part.jax_splits == whole.jax_splits                      # (0 for full history: everything comes from the one key)
+    # past 2^32: the terminal draw of the first root alone is at index root0 * mg * d
+    big = (1 << 32) - 6
+    assert big * 1 * d > 1 << 32 and big + B > 1 << 32                  # the row itself passes 2^32 too: it does not wrap
+    far = fresh().uz_solve(n, par, xt, root0=big)
+    assert not np.array_equal(far, want)
+    for r, k in ((2, 5), (6, 6)):                                       # (6, 6): rows 2^32 .. 2^32 + 5
+        assert np.array_equal(fresh().uz_solve(n, par, xt[r:r + k], root0=big + r), far[r:r + k]), (r, k)
+    # a second call of one oracle continues the key state, with or without root0
+    a, b = fresh(), fresh()
+    a.uz_solve(n, par, xt)
+    b.uz_solve(n, par, xt[:1], root0=9)
+    assert a.jax_splits == b.jax_splits
+    assert np.array_equal(a.uz_solve(n, par, xt[3:6], root0=3), b.uz_solve(n, par, xt, root0=0)[3:6])
