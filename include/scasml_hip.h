@@ -56,7 +56,10 @@ typedef struct {
     float clip;       /* norm_estimation (MLP.py:273-274) or uncertainty (ScaSML.py:282-284)*/
 } scasml_problem;
 
-/* Philox4x32-10 stream: counter = (quad, site, root0 + local root, stream), key = seed. */
+/* Philox4x32-10 stream: counter = (quad, site, root0 + local root, stream), key = seed.
+ * Stream ids: the solvers count their calls from 0 (one id per uz_solve); SCASML_STREAM_GP_SAMPLE is reserved for scasml_gp_sample, where
+ * root = sample index, site = 0 and quad q holds the normals of points 4q .. 4q+3 -- a solver would need 1.2e9 calls to reach it. */
+#define SCASML_STREAM_GP_SAMPLE 0x47505053u   /* "GPPS" */
 typedef struct {
     uint64_t seed;
     uint32_t stream;  /* advanced by the host once per solver call (replaces MLP.py:220 key splitting) */
@@ -458,6 +461,19 @@ int scasml_gp_cross_rows(int32_t d, double a, const float *x_dom, int32_t n_dom,
  * squares in registers; csrc/gp_variance.hip) -- no atomics, and a row's result is a function of that row, L and Mp alone, bit for bit: it does not
  * depend on n, on the row's position or on the other rows.  n = 0 does nothing. */
 int scasml_gp_variance(const double *L, int64_t Mp, double *rows, int64_t ld, int64_t n, double prior, double *var_out, void *stream);
+
+/* Added within ABI 7 (additive).  S draws from N(mean, Lc Lc^T) at n points, float64:
+ *   out[s*ld_out + i] = mean[i] + sum_{j <= i} Lc[i*np + j] * z(seed, sample0 + s, j),   i < n, s < S
+ * Lc: the lower Cholesky factor of the n x n joint covariance in an np x np row-major buffer, np a multiple of 32, identity-padded as scasml_cholesky
+ * leaves it; only its lower triangle is read (the strict upper triangle may hold anything).  z(seed, r, j) is component j % 4 of the Philox normals
+ * normal4(quad = j / 4, site = 0, root = r, stream = SCASML_STREAM_GP_SAMPLE, key = seed), widened to double -- on the host
+ * oracle.philox.normals(seed, SCASML_STREAM_GP_SAMPLE, [r], 0, n)[0][j].  They are drawn in registers and never stored: a workgroup owns 64 samples x
+ * 64 points, generates the 64 x 32 normal stage it needs and multiplies on v_mfma_f64_16x16x4_f64 (csrc/gp_sample.hip); tiles above the diagonal are
+ * skipped, the diagonal tiles masked.  No atomics; row s of `out` is a function of (Lc, mean, seed, sample0 + s) alone, bit for bit: it does not depend
+ * on S, on how a run of samples is split over calls or on the other samples.  Sample indices must stay below 2^32 (SCASML_ERR_UNSUPPORTED beyond);
+ * S = 0 does nothing. */
+int scasml_gp_sample(const double *Lc, int64_t np, int64_t n, const double *mean, uint64_t seed, int64_t sample0, int64_t S, double *out,
+                     int64_t ld_out, void *stream);
 
 /* ------------------------------------------------------------------ block-row distributed Gram / Cholesky / solves
  * For collocation sets whose K(phi, phi) does not fit one GPU (BASELINE configs[4]: 1e5 points, M = 350 000, 980 GB float64)

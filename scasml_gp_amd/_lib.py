@@ -20,6 +20,7 @@ EQ_CUBIC_REACTION_DIFFUSION = 1
 EQ_QUADRATIC_GRADIENT_REACTION_DIFFUSION = 2      # f(u, sum z, |z|^2): surrogate-free Picard kernels only
 # round16 bits of the as-coded GP entry points (include/scasml_hip.h); bit 2 means one thing for the Gram, Gram rows, cross rows and
 # float64 evaluation, another for the matrix-core evaluation
+STREAM_GP_SAMPLE = 0x47505053   # Philox stream id of scasml_gp_sample (SCASML_STREAM_GP_SAMPLE); the solvers count theirs from 0
 ROUND16_ENTRIES = 1       # every kernel entry rounded to float16
 ROUND16_OUTPUTS = 2       # evaluation: u_hat and eps_PDE leave as float16 values
 ROUND16_F16_OPS = 4       # Gram, Gram rows, cross rows, float64 evaluation: the float16 op sequence on float16 rows
@@ -117,6 +118,7 @@ SIGNATURES = {
     "scasml_gp_cross_rows": (C.c_int, [C.c_int32, C.c_double, C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_int32, C.c_int32,
                                        C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p]),
     "scasml_gp_variance": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_int64, C.c_double, C.c_void_p, C.c_void_p]),
+    "scasml_gp_sample": (C.c_int, [C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_uint64, C.c_int64, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p]),
     "scasml_gp_gram_rows": (C.c_int, [C.c_int32, C.c_double, C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_int64, C.c_int32, C.c_int64,
                                       C.c_void_p, C.c_int64, C.c_void_p]),
     "scasml_gp_gram_compat_rows": (C.c_int, [C.c_int32, C.c_double, C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_int64,

@@ -581,6 +581,173 @@ class GP(object):
         var = self.predict_variance(x_t_infer)
         return np.sqrt(np.maximum(var, 0.0)) if isinstance(var, np.ndarray) else var.clamp_min(0.0).sqrt()
 
+    # joint posterior (no counterpart in models/GP.py): covariance between evaluation points and draws from N(mean, cov)
+    def _rows_device(self, x):
+        """(n, d+1) numpy / torch -> (float32 CUDA rows, was_numpy, float16 rows), as predict_variance takes its points."""
+        torch = _lib.require_gpu()
+        was_numpy = not isinstance(x, torch.Tensor)
+        f16_rows = (np.asarray(x).dtype == np.float16) if was_numpy else x.dtype == torch.float16
+        xi = x if not was_numpy else torch.from_numpy(np.ascontiguousarray(np.asarray(x), dtype=np.float32))
+        xi = xi.to(device="cuda", dtype=torch.float32).contiguous()
+        if xi.dim() != 2 or xi.shape[1] != self.d + 1:
+            raise ValueError("points must have shape (n, %d), got %s" % (self.d + 1, tuple(xi.shape)))
+        return xi, was_numpy, bool(f16_rows)
+
+    def _solved_rows(self, L, xi, f16_rows, buf, var):
+        """buf[:len(xi)] <- (L^-1 K(phi, x_i))^T: op-0 feature rows solved in place by scasml_gp_variance (its variances, a by-product, go to var)."""
+        lib = _lib.load()
+        n, Mp = xi.shape[0], L.shape[0]
+        as_coded = self.compat == "reference"
+        r16 = self._gram_bits(self._xd, self._xb, f16_rows) if as_coded else 0
+        s = _lib.stream_ptr()
+        buf[:n].zero_()                                                # columns M .. Mp stay zero (L is the identity there)
+        for lo in range(0, n, 65535 * 16):
+            m = min(65535 * 16, n - lo)
+            _lib.check(lib.scasml_gp_cross_rows(self.d, self.a, _lib.ptr(self._xd), self.N_domain, _lib.ptr(self._xb) if self.N_boundary else None,
+                                                self.N_boundary, self.laplacian_idx.ctypes.data_as(C.c_void_p) if as_coded else None, r16,
+                                                0 if as_coded else 1, 0, _lib.ptr(xi[lo:]), m, self.d + 1, _lib.ptr(buf[lo:]), Mp, s), "gp_cross_rows")
+        _lib.check(lib.scasml_gp_variance(_lib.ptr(L), Mp, _lib.ptr(buf), Mp, n, 1.0, _lib.ptr(var), s), "gp_variance")
+        return buf[:n]
+
+    def _prior_block(self, xi, yi, f16_ops):
+        """kappa(x_i, y_j), (n, m) float64 on the device.  Documented operators: exp(-a |x - y|^2 / 2) in float64, the squared distance added
+        coordinate by coordinate.  As coded: the library's own op-0 entry for the pair, by kappa_kernel's route -- scasml_gp_cross_rows with the y
+        block as a domain set, whose first m columns are kappa -- walked in column blocks that keep its (n x 4 m) rows under
+        variance_buffer_bytes.  f16_ops (f16_graph, x AND y handed in as float16 arrays) selects the reference's float16 op sequence; it is decided
+        by the callers' dtypes, never by the values of a block, so every entry is a function of its own pair, whatever the block."""
+        torch = _lib.require_gpu()
+        lib = _lib.load()
+        n, m = xi.shape[0], yi.shape[0]
+        if self.compat is None:
+            x64, y64 = xi.to(torch.float64), yi.to(torch.float64)
+            dist = torch.zeros((n, m), dtype=torch.float64, device="cuda")
+            for k in range(self.d + 1):
+                diff = x64[:, k:k + 1] - y64[None, :, k]
+                dist.addcmul_(diff, diff)
+            return dist.mul_(-0.5 * self.a).exp_()
+        out = torch.empty((n, m), dtype=torch.float64, device="cuda")
+        r16 = _lib.ROUND16_ENTRIES | (_lib.ROUND16_F16_OPS | self._f16_extra if f16_ops else 0)
+        step = int(max(1, min(m, self.variance_buffer_bytes // (32 * n))))
+        rows = torch.empty((min(n, 65535 * 16), 4 * step), dtype=torch.float64, device="cuda")
+        for lo in range(0, m, step):
+            w = min(step, m - lo)
+            for r0 in range(0, n, rows.shape[0]):
+                h = min(rows.shape[0], n - r0)
+                _lib.check(lib.scasml_gp_cross_rows(self.d, self.a, _lib.ptr(yi[lo:]), w, None, 0, self.laplacian_idx.ctypes.data_as(C.c_void_p), r16, 0, 0,
+                                                    _lib.ptr(xi[r0:]), h, self.d + 1, _lib.ptr(rows), 4 * step, _lib.stream_ptr()), "gp_cross_rows")
+                out[r0:r0 + h, lo:lo + w] = rows[:h, :w]
+        return out
+
+    def predict_covariance(self, x_t_infer, y_t_infer=None):
+        '''(n, m) float64 posterior covariance  cov(x_i, y_j) = kappa(x_i, y_j) - (L^-1 K(phi, x_i))^T (L^-1 K(phi, y_j));  y = None means y = x
+        (NumPy in, NumPy out; CUDA tensor in, CUDA tensor out; the raw value, not clamped).
+
+        compat=None: the posterior covariance of u under the prior kappa given noisy observations of the collocation functionals.
+        compat="reference": the as-coded ANALOGUE, with the caveat of predict_variance -- the same formula on the matrices the reference's code
+        builds, which are not the Gram matrix and cross-covariances of one kernel: no positive semidefiniteness is guaranteed (sample_posterior's
+        jitter covers it).  The prior entry is then the library's own as-coded kappa for the pair (kappa_kernel's route); under f16_graph it follows the
+        float16 op sequence when x and y are both handed in as float16 arrays -- decided by the dtypes, not by the values.
+
+        Composed from what predict_variance uses: scasml_gp_cross_rows (op 0) into padded row buffers, scasml_gp_variance solves each in place
+        (rows <- rows L^-T), the prior block goes into C and scasml_gemm_nt_sub subtracts Vx Vy^T on the FP64 matrix cores (K = Mp, a fixed sum
+        order).  Every entry is a function of its own pair of points, bit for bit: a sub-selection, a permutation or another chunking returns the
+        same bits.  With y = None the solved rows are computed once, one triangle is computed and mirrored: C == C.T exactly, and the same bits as
+        predict_covariance(x, x).  diag(C) agrees with predict_variance to ROUNDING only -- that kernel sums the squares column by column in one
+        register, this one in the MFMA's 4-wide order.  n and m are walked in chunks so that both row buffers together stay under
+        ``variance_buffer_bytes``.'''
+        torch = _lib.require_gpu()
+        lib = _lib.load()
+        L = self._variance_factor()
+        xi, was_numpy, f16x = self._rows_device(x_t_infer)
+        symmetric = y_t_infer is None
+        yi, f16y = (xi, f16x) if symmetric else self._rows_device(y_t_infer)[::2]
+        n, m, Mp = xi.shape[0], yi.shape[0], L.shape[0]
+        Cm = torch.empty((n, m), dtype=torch.float64, device="cuda")
+        if n == 0 or m == 0:
+            return Cm.cpu().numpy() if was_numpy else Cm
+        rows_cap = int(max(2, self.variance_buffer_bytes // (8 * Mp)))
+        s = _lib.stream_ptr()
+        f16_ops = self.f16_graph and f16x and f16y
+
+        def subtract(block, Vx, Vy, lower_only):
+            # lower_only (a diagonal block of the symmetric case): the 64 x 64 tiles above the 256-row block diagonal are skipped, then mirrored over
+            _lib.check(lib.scasml_gemm_nt_sub(_lib.ptr(block), block.stride(0), block.shape[0], block.shape[1], _lib.ptr(Vx), Mp, _lib.ptr(Vy), Mp, Mp,
+                                              0, 1 if lower_only else 0, 0, s), "gemm_nt_sub")
+
+        if symmetric and n <= rows_cap:
+            Vx = self._solved_rows(L, xi, f16x, torch.empty((n, Mp), dtype=torch.float64, device="cuda"), torch.empty(n, dtype=torch.float64, device="cuda"))
+            Cm.copy_(self._prior_block(xi, xi, f16_ops))
+            subtract(Cm, Vx, Vx, True)
+        else:
+            cx = int(min(n, rows_cap // 2))
+            cy = int(min(m, rows_cap // 2))
+            bx = torch.empty((cx, Mp), dtype=torch.float64, device="cuda")
+            by = torch.empty((cy, Mp), dtype=torch.float64, device="cuda")
+            var = torch.empty(max(cx, cy), dtype=torch.float64, device="cuda")
+            for i0 in range(0, n, cx):
+                Vx = self._solved_rows(L, xi[i0:i0 + cx], f16x, bx, var)
+                for j0 in range(0, m, cy):
+                    if symmetric and j0 > i0:                          # cx == cy: the blocks above the diagonal are mirrored
+                        break
+                    diag = symmetric and j0 == i0
+                    Vy = Vx if diag else self._solved_rows(L, yi[j0:j0 + cy], f16y, by, var)
+                    block = Cm[i0:i0 + cx, j0:j0 + cy]
+                    block.copy_(self._prior_block(xi[i0:i0 + cx], yi[j0:j0 + cy], f16_ops))
+                    subtract(block, Vx, Vy, diag)
+        if symmetric:
+            Cm = torch.tril(Cm) + torch.tril(Cm, -1).t()
+        return Cm.cpu().numpy() if was_numpy else Cm
+
+    def sample_posterior(self, x_t_infer, n_samples, seed=0, jitter=None, sample0=0):
+        '''(n_samples, n) float64 draws from N(mean(x), cov(x, x) + jitter I) (NumPy in, NumPy out; CUDA tensor in, CUDA tensor out).
+
+        mean = predict(x) widened to float64 -- the surrogate the solvers use, float16 output values as coded included; cov = predict_covariance(x).
+        The covariance is copied into an identity-padded buffer and factored by scasml_cholesky with nugget = jitter (default: self.nugget, the
+        observation noise the model already assumes, which also keeps the as-coded analogue factorable); a non-positive pivot raises ValueError.
+        scasml_gp_sample then forms mean + Lc z on the FP64 matrix cores with Philox normals drawn inside the kernel: draw s is a function of
+        (x, seed, sample0 + s) alone, bit for bit, so the chunks n_samples is walked in (host output: the device holds one chunk at a time) cannot change it and
+        ``sample0`` continues a stream of draws.  n is bounded by the n x n factor: 8 np^2 bytes (np = n rounded up to 32) must fit ``variance_buffer_bytes``.'''
+        torch = _lib.require_gpu()
+        lib = _lib.load()
+        n_samples, sample0 = int(n_samples), int(sample0)
+        if n_samples < 0 or sample0 < 0:
+            raise ValueError("n_samples and sample0 must not be negative")
+        jitter = float(self.nugget if jitter is None else jitter)
+        was_numpy = not isinstance(x_t_infer, torch.Tensor)
+        # the caller's rows in their own dtype, on the device once (float16 rows stay float16 rows for predict and the as-coded entries)
+        xdev = torch.from_numpy(np.ascontiguousarray(np.asarray(x_t_infer))).cuda() if was_numpy else x_t_infer
+        if xdev.dim() != 2 or xdev.shape[1] != self.d + 1:
+            raise ValueError("points must have shape (n, %d), got %s" % (self.d + 1, tuple(xdev.shape)))
+        n = xdev.shape[0]
+        npad = _round_up(max(n, 1), 32)
+        if 8 * npad * npad > self.variance_buffer_bytes:
+            raise ValueError("sample_posterior factors an n x n covariance: n = %d needs %d bytes, variance_buffer_bytes = %d allows n <= %d" % (
+                n, 8 * npad * npad, self.variance_buffer_bytes, int(np.sqrt(self.variance_buffer_bytes // 8)) // 32 * 32))
+        if n == 0 or n_samples == 0:
+            return np.empty((n_samples, n)) if was_numpy else torch.empty((n_samples, n), dtype=torch.float64, device="cuda")
+        mean = self.predict(xdev)[:, 0].to(torch.float64).contiguous()
+        Lc = torch.eye(npad, dtype=torch.float64, device="cuda")
+        Lc[:n, :n] = self.predict_covariance(xdev)
+        info = torch.zeros(1, dtype=torch.int32, device="cuda")
+        s = _lib.stream_ptr()
+        _lib.check(lib.scasml_cholesky(_lib.ptr(Lc), npad, jitter, _lib.ptr(info), s), "cholesky(cov)")
+        if int(info.item()) != 0:
+            raise ValueError("cov(x, x) + jitter I is not positive definite at jitter = %g (pivot %d of %d): pass a larger jitter" % (
+                jitter, int(info.item()), n))
+        seed = int(seed) & 0xFFFFFFFFFFFFFFFF
+        if not was_numpy:                                              # the caller's tensor is the whole output anyway: one launch
+            out = torch.empty((n_samples, n), dtype=torch.float64, device="cuda")
+            _lib.check(lib.scasml_gp_sample(_lib.ptr(Lc), npad, n, _lib.ptr(mean), seed, sample0, n_samples, _lib.ptr(out), n, s), "gp_sample")
+            return out
+        # host output: the device holds one chunk of draws at a time, under variance_buffer_bytes
+        chunk = int(min(n_samples, max(64, self.variance_buffer_bytes // (8 * n) // 64 * 64)))
+        out, dev = np.empty((n_samples, n)), torch.empty((chunk, n), dtype=torch.float64, device="cuda")
+        for lo in range(0, n_samples, chunk):
+            c = min(chunk, n_samples - lo)
+            _lib.check(lib.scasml_gp_sample(_lib.ptr(Lc), npad, n, _lib.ptr(mean), seed, sample0 + lo, c, _lib.ptr(dev), n, s), "gp_sample")
+            out[lo:lo + c] = dev[:c].cpu().numpy()
+        return out
+
     def compute_gradient(self, x_t_infer, sol_infer=None):
         '''(n, d+1) gradient of the posterior mean, time derivative last (models/GP.py:673-687).'''
         torch = _lib.require_gpu()
