@@ -258,11 +258,20 @@ int scasml_gp_eval(const scasml_gp_model *gp_h, const float *points, int64_t n_i
                    float *out4, float *lap, void *stream);
 
 /* Same, for the site-major point buffer of scasml_picard_tree: rows [s*rows_per_site, (s+1)*rows_per_site) are
- * tree site s; site_u_only[s] (device bytes, from scasml_plan_site_kinds): 0 = every output needed; 1 = only u_hat is
- * consumed (the root, ScaSML.py:303) -- its rows get u_hat only (div, eps, dt = 0), which halves the epilogue work;
- * 3 = only u_hat AND every row of the site has t = T_terminal of scasml_gp_pack exactly (terminal samples, ScaSML.py:61):
- * a quarter of the full epilogue, used when rows_per_site is a multiple of 32 (otherwise treated as 1); 4 = u_hat and
- * div_x u_hat are consumed (eps, dt = 0); 2 = skip the site. */
+ * tree site s; site_u_only[s] (device bytes, from scasml_plan_site_kinds, one per site, ceil(n_inf / rows_per_site) of them)
+ * says which outputs the caller consumes there: 0 = all four; 1 = u_hat only (the root, ScaSML.py:303); 3 = u_hat only AND
+ * every row of the site has t = T_terminal of scasml_gp_pack exactly (terminal samples, ScaSML.py:61); 4 = u_hat and
+ * div_x u_hat; 2 = nothing (another rank's site).
+ * A consumed output has the bits scasml_gp_eval gives for the same row, with one exception: a kind-3 site whose rows fill
+ * whole 32-row wavefront tiles (rows_per_site a multiple of 32) takes the folded terminal form, a quarter of the full
+ * epilogue, whose u_hat agrees with the full form's to rounding only.  Outputs a site's kind does not consume are
+ * UNSPECIFIED: the 16-bit kernels (split 22, 3, 2) drop the sums a 32-row tile does not need only when the tile lies in
+ * one site or in two u_hat-only ones, and then store eps_PDE as the residual of (u_hat, 0, 0, Lap = -a d u_hat), not 0; a
+ * tile that straddles other kinds is evaluated in full.  Kind-2 rows are skipped -- out4 left as it was -- only by the
+ * 16-bit kernels and only per whole workgroup (128, 256 or 384 rows, by d and split) that lies inside kind-2 sites; other
+ * kind-2 rows are evaluated like any row (their point rows must be readable; their values affect no other row).
+ * rows_per_site < 32 and the FP32 kernel (split 0) ignore the kinds and evaluate every row in full.  site_u_only = NULL
+ * is scasml_gp_eval without `lap`; with kinds, rows_per_site < 1 is SCASML_ERR_ARG. */
 int scasml_gp_eval_sites(const scasml_gp_model *gp_h, const float *points, int64_t n_inf, int64_t rows_per_site,
                          const uint8_t *site_u_only, float *out4, void *stream);
 

@@ -248,6 +248,24 @@ def _doc_setup(d, f16_colloc):
     return gp, ora, X, mag, want
 
 
+@functools.lru_cache(maxsize=2)
+def _doc_lap_magnitude(d, f16_colloc):
+    """What a rounding error of the Laplacian is relative to: the absolute values of the terms its epilogue adds (gp_eval.hip:10-15),
+    sum_j kappa (|L| |E|_abs + 2 a (|cL| (2 |L| + a d) + |cS s|)) with |L| = a^2 rho^2 + a d and |E|_abs = |c0| + |cL| |L| + |ct p| + |cS s|."""
+    _, ora, X, _, _ = _doc_setup(d, f16_colloc)
+    a, N, Nb = ora.a, ora.N_domain, ora.N_boundary
+    rv = np.abs(ora.right_vector[:, 0])
+    c0, cb, cL, ct, cS = rv[:N], rv[N:N + Nb], rv[N + Nb:2 * N + Nb], rv[2 * N + Nb:3 * N + Nb], rv[3 * N + Nb:]
+    kap, rho2, S, rt = ora._pairs(X, ora.x_t_domain)
+    L, p, s = a * a * rho2 + a * d, np.abs(a * rt), np.abs(a * S)
+    E = c0[None, :] + cL[None, :] * L + ct[None, :] * p + cS[None, :] * s
+    magL = (kap * (L * E + 2 * a * (cL[None, :] * (2 * L + a * d) + cS[None, :] * s))).sum(1)
+    if Nb:
+        kap, rho2, _, _ = ora._pairs(X, ora.x_t_boundary)
+        magL = magL + (kap * (a * a * rho2 + a * d) * cb[None, :]).sum(1)
+    return magL
+
+
 def _doc_raw(gp, X, split, f16_colloc):
     """(out4, lap) straight from scasml_gp_eval with the model's split set explicitly: the mode asked for is the mode that runs (the
     library refuses a split it cannot serve rather than demoting it)."""
@@ -269,12 +287,14 @@ def _doc_raw(gp, X, split, f16_colloc):
 def test_documented_operators_match_the_float64_statement(d, mode):
     split, f16_colloc, tol_u, tol_p = DOC_MODES[mode]
     gp, ora, X, mag, want = _doc_setup(d, f16_colloc)
-    out4, _ = _doc_raw(gp, X, split, f16_colloc)
+    out4, lap = _doc_raw(gp, X, split, f16_colloc)
     magp = mag * (1 + ora.a * (1 + d))                    # derivative features carry factors of a, a d
     assert np.all(np.abs(out4[:, 0] - want["u"]) <= tol_u * mag), np.max(np.abs(out4[:, 0] - want["u"]) / mag)
     assert np.all(np.abs(out4[:, 1] - want["div"]) <= tol_p * magp)
     assert np.all(np.abs(out4[:, 2] - want["eps"]) <= tol_p * magp)
     assert np.all(np.abs(out4[:, 3] - want["dt"]) <= tol_p * magp)
+    magL = _doc_lap_magnitude(d, f16_colloc)
+    assert np.all(np.abs(lap - want["lap"]) <= tol_p * magL), np.max(np.abs(lap - want["lap"]) / magL)
     _prefixes_are_bitwise(lambda x: _doc_raw(gp, x, split, f16_colloc), X)
 
 
