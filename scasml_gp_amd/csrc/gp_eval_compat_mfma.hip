@@ -26,7 +26,10 @@
 // statement's where the float32 value lands within ~2^-20 of a float16 midpoint (about 1 entry in 500); tests bound the effect.
 //
 // Cost model: the launch time is vector time PLUS matrix time (the chip's clock follows the MFMA density), so the levers are fewer instructions of
-// either kind, not their arrangement; the measurements and the rejected arrangements are in profiles/HISTORY.md (4.4).
+// either kind, not their arrangement; the measurements and the rejected arrangements are in profiles/HISTORY.md (4.4).  Matrix side: 2 KS MFMAs
+// per stage for x.y' and one for G -- 2 KS - 1 where the tail of the point is short enough to share the last K-step with its own low parts
+// (compat_tail_packed; d = 100: 14 per stage, the minimum for 104 + 102 + 14 live columns; profiles/r07_kpack_ab.txt).  Vector side, per pair of
+// the full form: 26 / 13 / 12 instructions (al / ys / xs).
 //
 // Structure (as gp_eval_bf16.hip): 4-wave workgroups, 32 points per wave held in VGPRs as two fp16 planes for the whole sweep;
 // the unit of work is a STAGE = (collocation tile of 32 rows, geometry): [KS KiB A fragments | 1 KiB Q fragment | 1 KiB row
@@ -35,7 +38,8 @@
 //     full (u, dt, div, lap -> eps_PDE)   al, ys, xs on domain tiles;  al, xs on boundary tiles
 //     u only / u and div                  al, ys on domain tiles;      al on boundary tiles
 // Template parameters: KS K-steps of 16, BPC workgroups per CU, R16 the per-entry float16 rounding (the reference's code; off = the geometry mode's
-// factored epilogue, compat_epilogue_fact), PLANES float16 planes of the evaluation point (2: products exact to 2^-22; 1: the geometry mode's option).
+// factored epilogue, compat_epilogue_fact), PLANES float16 planes of the evaluation point (2: products exact to 2^-22; 1: the geometry mode's option),
+// PACK the tail-packed column map (two planes only; its own entry point, gp_eval_compat_mfma_tail_kernel).
 #include <stdlib.h>
 #include <type_traits>
 
@@ -68,6 +72,7 @@ struct GpCompatArgs {
     int64_t rows_per_site;
     const int32_t *site_order;   // scasml_gp_eval_compat_site_list: the sites to evaluate, in launch order (a 32-row wavefront tile is one site); null: all rows
     int32_t n_listed;
+    int32_t tail_packed;         // compat_tail_packed(d, kp): the column map of the model
 };
 
 // round two float32 to float16 (RNE) in one instruction; R16 = false keeps them (development / parity of the formulas)
@@ -93,10 +98,27 @@ __device__ __forceinline__ float pin(float x) {
     return x;
 }
 
-// one collocation tile's x.y' on the fp16 matrix cores: 2 MFMAs per K-step (point planes h, l against the one collocation plane).
+// The K columns of a stage.  K-steps 0 .. KS-2 hold the first 16 (KS - 1) columns of the point, split by half-wave as the fragments are (slot c
+// of step s = column (c / 8) 8 (KS - 1) + 8 s + c % 8: each half-wave reads one contiguous run of the point's row); the last K-step (slot c =
+// column 16 (KS - 1) + c) holds the r = max(0, d + 1 - 16 (KS - 1)) columns that are left and the three constant columns (collocation side: the two halves of
+// k1 a^2 |y|^2 and a 1 against k1 a^2 |x|^2).  Where the tail is short, 2 r + 4 <= 16, the low plane of the last step moves into the free
+// slots of the high one and the step is ONE MFMA (d = 100: 13 + 1 (G) per stage, not 15):
+//                            slot   0 .. 5          6      7      8 .. 13        14         15
+//     tail-packed  point     x_h (zeros past r)     1      1      x_l            |x|^2_h    |x|^2_l   (PLANES = 1: x_l = 0, |x|^2_l in acc0)
+//                  row       y                      |y|^2_h |y|^2_l  y (again)     1          1
+//     otherwise    point     x (13 at the most) ..  1  1  |x|^2   in slots 13, 14, 15; two planes as in every other step
+//                  row       y                  ..  |y|^2_h  |y|^2_l  1
+// One rule for the pack and for the launch:
+static inline bool compat_tail_packed(int d, int kp) {
+    const int r = d + 1 - (kp - 16);
+    return 2 * (r > 0 ? r : 0) + 4 <= 16;
+}
+
+// one collocation tile's x.y' on the fp16 matrix cores: 2 MFMAs per K-step (point planes h, l against the one collocation plane), 1 in a
+// tail-packed last step (PACK).
 // PLANES = 1 (the geometry mode's option, round16 bit 2): the high plane only -- the point's coordinates enter x.y' rounded to float16
 // (|x|^2 stays float32: the low part of its column is the accumulator's start value acc0), half the MFMAs.
-template <int KS, int PLANES>
+template <int KS, int PLANES, bool PACK>
 __device__ __forceinline__ void compat_mfma_lam(const float4 *lds_a, const s16x8 (&xb)[PLANES][KS], f32x16 &acc, int lane, float acc0) {
 #pragma unroll
     for (int r = 0; r < 16; ++r) acc[r] = acc0;
@@ -117,9 +139,11 @@ __device__ __forceinline__ void compat_mfma_lam(const float4 *lds_a, const s16x8
         Frag b0;
         b0.v = xb[0][s];
         if constexpr (PLANES == 2) {
-            Frag b1;
-            b1.v = xb[1][s];
-            acc = __builtin_amdgcn_mfma_f32_32x32x16_f16(a[cur].h, b1.h, acc, 0, 0, 0);   // small terms first
+            if (!(PACK && s == KS - 1)) {
+                Frag b1;
+                b1.v = xb[1][s];
+                acc = __builtin_amdgcn_mfma_f32_32x32x16_f16(a[cur].h, b1.h, acc, 0, 0, 0);   // small terms first
+            }
         }
         acc = __builtin_amdgcn_mfma_f32_32x32x16_f16(a[cur].h, b0.h, acc, 0, 0, 0);
         __builtin_amdgcn_sched_barrier(0);
@@ -312,8 +336,9 @@ __device__ __forceinline__ void compat_epilogue_fact(const float *rows_lds, cons
 // Stage block, in floats (scasml_gp_compat_pack_mfma): KS*256 planes | 256 Q fragment | 256 row constants (32 x 8) = (KS + 2) KiB
 constexpr int kStageTail = 256 + 256;
 
-template <int KS, int BPC, bool R16, int PLANES>
-__global__ __launch_bounds__(256, BPC) void gp_eval_compat_mfma_kernel(const GpCompatArgs g) {
+// The body of both kernels below: PACK = the tail-packed column map (compat_tail_packed).
+template <int KS, bool R16, int PLANES, bool PACK>
+__device__ __forceinline__ void compat_mfma_sweep(const GpCompatArgs g) {
     static_assert(PLANES == 2 || !R16, "the as-coded form keeps both point planes");
     // three slots: stage s is read while s + 1 has landed or lands and s + 2 is issued into the slot stage s - 1 was read from, which
     // every wave left before the barrier that ended step s - 1
@@ -350,6 +375,9 @@ __global__ __launch_bounds__(256, BPC) void gp_eval_compat_mfma_kernel(const GpC
         const int64_t vw = blk * WPB + wv, vs = vw / wps;
         p0 = vs < g.n_listed ? (int64_t)g.site_order[vs] * g.rows_per_site + (vw - vs * wps) * 32 : g.n_inf;   // past the list: shadow rows, never stored
     }
+
+    // the wave's first row is uniform: scalar registers
+    p0 = ((int64_t)__builtin_amdgcn_readfirstlane((int32_t)(p0 >> 32)) << 32) | (uint32_t)__builtin_amdgcn_readfirstlane((int32_t)p0);
 
     // Monte-Carlo sample sharding: a workgroup that lies wholly inside sites of other ranks has nothing to do
     if (!g.site_order && g.site_kinds && g.rows_per_site >= 32) {
@@ -425,11 +453,11 @@ __global__ __launch_bounds__(256, BPC) void gp_eval_compat_mfma_kernel(const GpC
     stage(0);
     if (n_stages > 1) stage(1);
 
-    // ---- this wave's 32 points: fp16 planes (h, l) of 2 a^2 q x, the constants (1, 1, k1 a^2 |x|^2) in the last three columns
+    // ---- this wave's 32 points: fp16 planes (h, l) of 2 a^2 q x and the constants (1, 1, k1 a^2 |x|^2), in the column map of compat_tail_packed
     const float qs = 0.5f * 1.44269504088896341f / g.a, k1 = -qs;
     const float hh = (float)g.d / (float)kHutch;
     const float ha2 = hh * g.a * g.a;
-    s16x8 xb[PLANES][KS];
+    s16x8 xb[PLANES][KS];       // PACK: xb[1][KS - 1] stays unset, no MFMA reads it
     float acc0 = 0.0f;          // PLANES == 1: the low part of the |x|^2 column, which the dropped plane would have carried
     CompatPoint pt;
     Frag qa[1], qb[1];          // B fragments of the Q products: components i_j + 1 (al, xs) and i_j (ys)
@@ -437,32 +465,38 @@ __global__ __launch_bounds__(256, BPC) void gp_eval_compat_mfma_kernel(const GpC
         int64_t row = p0 + col;
         if (row >= g.n_inf) row = g.n_inf - 1;   // shadow rows, never stored
         const float *prow = g.points + row * g.kp;
-        const int kbase = half * (8 * KS);
-        const float4 *src = reinterpret_cast<const float4 *>(prow + kbase);
+        // a half-wave holds slots 8 half .. 8 half + 7 of every K-step: its own run of 8 (KS - 1) columns, then its half of the last step's
+        // sixteen -- or, tail-packed, the first eight of them in both halves
+        const float4 *src = reinterpret_cast<const float4 *>(prow + half * (8 * (KS - 1)));
+        // (one plane: packing saves no MFMA, so one kernel serves both maps; its upper half-wave reads its own eight columns in either,
+        // which in a packed tail are the point's zero padding)
+        const float4 *src_tail = reinterpret_cast<const float4 *>(prow + 16 * (KS - 1) + (PACK ? 0 : 8 * half));
         float pn = 0.0f, ps = 0.0f;
         const float ptime = prow[g.d], px0 = prow[0];
         const float fold = 2.0f * g.a * g.a * qs;
+        auto lo = [](float v) { return v - (float)(_Float16)v; };
         auto make_planes = [&](const float (&t)[8], Frag &fh, Frag &fl) {
 #pragma unroll
             for (int c = 0; c < 4; ++c) {
-                const float h0 = (float)(_Float16)t[2 * c], h1 = (float)(_Float16)t[2 * c + 1];
                 fh.u[c] = pack_h2(t[2 * c], t[2 * c + 1]);
-                fl.u[c] = pack_h2(t[2 * c] - h0, t[2 * c + 1] - h1);
+                fl.u[c] = pack_h2(lo(t[2 * c]), lo(t[2 * c + 1]));
             }
         };
         float tlast[8];
 #pragma unroll
         for (int s = 0; s < KS; ++s) {
-            const float4 q0 = src[2 * s], q1 = src[2 * s + 1];
+            const bool last = s == KS - 1;
+            const float4 q0 = last ? src_tail[0] : src[2 * s], q1 = last ? src_tail[1] : src[2 * s + 1];
             const float e[8] = {q0.x, q0.y, q0.z, q0.w, q1.x, q1.y, q1.z, q1.w};
             float t[8];
 #pragma unroll
             for (int c2 = 0; c2 < 8; ++c2) {
-                pn = fmaf(e[c2], e[c2], pn);
-                ps += e[c2];
+                const float w = (PACK && last && half) ? 0.0f : e[c2];   // a packed tail is read by both halves and counted once
+                pn = fmaf(w, w, pn);
+                ps += w;
                 t[c2] = fold * e[c2];
             }
-            if (s == KS - 1) {
+            if (last) {
 #pragma unroll
                 for (int c2 = 0; c2 < 8; ++c2) tlast[c2] = t[c2];
             } else {
@@ -474,15 +508,36 @@ __global__ __launch_bounds__(256, BPC) void gp_eval_compat_mfma_kernel(const GpC
         }
         pn += __shfl_xor(pn, 32);
         ps += __shfl_xor(ps, 32);
-        tlast[5] = half ? 1.0f : tlast[5];
-        tlast[6] = half ? 1.0f : tlast[6];
-        tlast[7] = half ? k1 * g.a * g.a * pn : tlast[7];
-        {
+        const float x2 = k1 * g.a * g.a * pn;
+        if constexpr (PLANES == 1) {
+            // the high plane alone, in either map, by selects: packed  half 0 = (x_h[0..5], 1, 1), half 1 = (0 .., |x|^2_h, 0)
+            const bool packed = g.tail_packed != 0;
+            tlast[5] = half ? (packed ? 0.0f : 1.0f) : tlast[5];
+            tlast[6] = half ? (packed ? x2 : 1.0f) : (packed ? 1.0f : tlast[6]);
+            tlast[7] = half ? (packed ? 0.0f : x2) : (packed ? 1.0f : tlast[7]);
             Frag fh, fl;
             make_planes(tlast, fh, fl);
             xb[0][KS - 1] = fh.v;
-            if constexpr (PLANES == 2) xb[1][KS - 1] = fl.v;
-            else acc0 = k1 * g.a * g.a * pn - (float)(_Float16)(k1 * g.a * g.a * pn);   // both halves: every row of this lane's column
+            acc0 = lo(x2);                              // both halves: every row of this lane's column
+        } else if constexpr (PACK) {
+            // one fragment: half 0 = (x_h[0..5], 1, 1), half 1 = (x_l[0..5], |x|^2_h, |x|^2_l); columns past the tail are zero in the point
+            Frag f;
+#pragma unroll
+            for (int c = 0; c < 3; ++c) {
+                const uint32_t h2 = pack_h2(tlast[2 * c], tlast[2 * c + 1]);
+                const uint32_t l2 = pack_h2(lo(tlast[2 * c]), lo(tlast[2 * c + 1]));
+                f.u[c] = half ? l2 : h2;
+            }
+            f.u[3] = half ? pack_h2(x2, lo(x2)) : pack_h2(1.0f, 1.0f);
+            xb[0][KS - 1] = f.v;
+        } else {
+            tlast[5] = half ? 1.0f : tlast[5];
+            tlast[6] = half ? 1.0f : tlast[6];
+            tlast[7] = half ? x2 : tlast[7];
+            Frag fh, fl;
+            make_planes(tlast, fh, fl);
+            xb[0][KS - 1] = fh.v;
+            xb[1][KS - 1] = fl.v;
         }
         pt.sx = g.a * (ps - ptime);           // the row sum includes t
         pt.tx = g.a * ptime;
@@ -540,7 +595,7 @@ __global__ __launch_bounds__(256, BPC) void gp_eval_compat_mfma_kernel(const GpC
         if (s_now + AHEAD < n_stages) stage(s_now + AHEAD);
         const float *base = lds + slot * STAGE;
         if (region & 1) {
-            compat_mfma_lam<KS, PLANES>(reinterpret_cast<const float4 *>(base), xb, acc, lane, acc0);
+            compat_mfma_lam<KS, PLANES, PACK>(reinterpret_cast<const float4 *>(base), xb, acc, lane, acc0);
             if constexpr (NEEDG) {
                 Frag aq;
                 aq.f = reinterpret_cast<const float4 *>(base + KS * 256)[lane];
@@ -580,7 +635,11 @@ __global__ __launch_bounds__(256, BPC) void gp_eval_compat_mfma_kernel(const GpC
     const float dt = at + __shfl_xor(at, 32);
     const float dv = ad + __shfl_xor(ad, 32);
     const float lp = al + __shfl_xor(al, 32);
-    const int64_t row = p0 + col;
+    // tail-packed as-coded form: the output row is formed again from the scalar p0, not kept in two registers through the sweep (KS = 7 sits at
+    // 128 registers and spilled exactly this pair); the other instances allocate better with the prologue's value kept
+    int col_out = col;
+    if constexpr (R16) asm volatile("" : "+v"(col_out));
+    const int64_t row = p0 + col_out;
     if (half == 0 && row < g.n_inf) {
         if (g.round_out) u = (float)(_Float16)u;                               // predict(...).astype(float16), models/GP.py:671
         float eps = dt + g.mu * dv + 0.5f * g.sigma * g.sigma * lp + eq_f<float>(g.eq_id, u, g.sigma * dv, g.sigma, (float)g.d);   // :767-768
@@ -590,10 +649,21 @@ __global__ __launch_bounds__(256, BPC) void gp_eval_compat_mfma_kernel(const GpC
     }
 }
 
+// Two entry points, one per column map, chosen by the launch (launch_compat): the long-tail map keeps its name and its 2 KS MFMAs per stage
+template <int KS, int BPC, bool R16, int PLANES>
+__global__ __launch_bounds__(256, BPC) void gp_eval_compat_mfma_kernel(const GpCompatArgs g) {
+    compat_mfma_sweep<KS, R16, PLANES, false>(g);
+}
+
+template <int KS, int BPC, bool R16, int PLANES>
+__global__ __launch_bounds__(256, BPC) void gp_eval_compat_mfma_tail_kernel(const GpCompatArgs g) {
+    compat_mfma_sweep<KS, R16, PLANES, true>(g);
+}
+
 // ---------------------------------------------------------------------------------------------------------------- pack
 // One thread per collocation row: the three stage blocks of its tile (planes in MFMA A-fragment order, Q fragment, row constants).
 __global__ void gp_compat_pack_mfma_kernel(int d, float a, const float *x_dom, int n_dom, const float *x_bdy, int n_bdy, const double *rv,
-                                           CompatIdxF ix, float *model, int n_pad, int kp) {
+                                           CompatIdxF ix, float *model, int n_pad, int kp, int packed) {
     const int j = blockIdx.x * blockDim.x + threadIdx.x;
     if (j >= n_pad) return;
     const int N = n_dom + n_bdy, D = d + 1, KS = kp / 16;
@@ -623,11 +693,18 @@ __global__ void gp_compat_pack_mfma_kernel(int d, float a, const float *x_dom, i
         uint16_t *planes = reinterpret_cast<uint16_t *>(blk);
         // geometry g's collocation row: al y, ys y' = (y_1, .., t, y_0), xs y'' = (t, y_0, .., y_{d-1})
         auto yg = [&](int k) { return g == 0 ? y(k) : (g == 1 ? y((k + 1) % D) : y((k + D - 1) % D)); };
-        for (int k = 0; k < kp; ++k) {
-            const float v = k <= d ? yg(k) : (k == kp - 3 ? (float)ayh : (k == kp - 2 ? ayl : (k == kp - 1 ? 1.0f : 0.0f)));
-            const int h = k / (kp / 2), kk = k % (kp / 2);
-            const int64_t e = (((int64_t)(kk / 8)) * 64 + h * 32 + i) * 8 + (kk & 7);
-            planes[e] = __builtin_bit_cast(unsigned short, (_Float16)v);
+        // K-step s, slot c (compat_tail_packed): lane (c / 8) * 32 + i of the step's A fragment, element c % 8
+        for (int s = 0; s < KS; ++s) {
+            for (int c = 0; c < 16; ++c) {
+                const int k = s < KS - 1 ? (c >> 3) * 8 * (KS - 1) + 8 * s + (c & 7)
+                                         : 16 * s + (packed && c >= 8 ? c - 8 : c);       // a packed tail meets the point's low parts too
+                float v = k <= d ? yg(k) : 0.0f;
+                if (s == KS - 1) {
+                    if (packed) v = (c & 7) < 6 ? v : (c == 6 ? (float)ayh : (c == 7 ? ayl : 1.0f));
+                    else v = c < 13 ? v : (c == 13 ? (float)ayh : (c == 14 ? ayl : 1.0f));
+                }
+                planes[(((int64_t)s * 64 + (c >> 3) * 32 + i) * 8) + (c & 7)] = __builtin_bit_cast(unsigned short, (_Float16)v);
+            }
         }
         // Q fragment (row side): half 0 = (y_0..4, 1, 1, PY_h), half 1 = (y_0..4, PY_l, 0, 0); components i_j + 1 (al, ys) or i_j (xs)
         float yq[kHutch], nq = 0.0f, sq = 0.0f;
@@ -679,10 +756,11 @@ __global__ void gp_compat_pack_mfma_kernel(int d, float a, const float *x_dom, i
     }
 }
 
-template <int KS, bool R16, int PLANES>
+template <int KS, bool R16, int PLANES, bool PACK>
 static int launch_compat(const GpCompatArgs &g, hipStream_t s) {
     // registers: 4 KS per point plane + ~72 (as-coded, reads not run ahead) / ~90 (geometry mode) for accumulators, Q fragments, row
-    // constants and temporaries
+    // constants and temporaries.  A packed tail frees the four of the last low-plane fragment; the estimate (and with it BPC) stays the long-tail
+    // one for both maps: as coded, KS = 7 is 128 registers without scratch in either (tests/test_kpack_registers.py)
     constexpr int REGS = 4 * PLANES * KS + (R16 ? 72 : 90);
     constexpr size_t lds_bytes = SCASML_COMPAT_NSLOT * (size_t)(KS * 256 + kStageTail) * sizeof(float);
     constexpr int BPC_REGS = REGS <= 128 ? 4 : (REGS <= 164 ? 3 : 2), BPC_LDS = (int)(160 * 1024 / lds_bytes);
@@ -692,7 +770,9 @@ static int launch_compat(const GpCompatArgs &g, hipStream_t s) {
     if (blocks == 0) return 0;
     if (blocks > 0x7FFFFFFF) return fail(SCASML_ERR_UNSUPPORTED, "gp_eval_compat_sites: too many points");
     static_assert(lds_bytes * BPC <= 160 * 1024, "LDS slots exceed 160 KiB");
-    auto kern = gp_eval_compat_mfma_kernel<KS, BPC, R16, PLANES>;
+    void (*kern)(const GpCompatArgs) = gp_eval_compat_mfma_kernel<KS, BPC, R16, PLANES>;
+    if constexpr (PACK) kern = gp_eval_compat_mfma_tail_kernel<KS, BPC, R16, PLANES>;
+    static_assert(PLANES == 2 || !PACK, "one plane: one kernel for both column maps");
     if (lds_bytes > 64 * 1024) {
         if (hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes) != hipSuccess)
             return fail(SCASML_ERR_HIP, "gp_eval_compat_sites: cannot reserve %zu bytes of LDS", lds_bytes);
@@ -703,9 +783,14 @@ static int launch_compat(const GpCompatArgs &g, hipStream_t s) {
 
 template <bool R16, int PLANES>
 static int launch_compat_ks(const GpCompatArgs &g, hipStream_t s) {
+    const bool packed = PLANES == 2 && g.tail_packed;       // one plane: the kernel reads the map from g
     switch (g.kp / 16) {
 #define SCASML_CASE(K) \
-    case K: return launch_compat<K, R16, PLANES>(g, s);
+    case K:                                                                                \
+        if constexpr (PLANES == 2) {                                                       \
+            if (packed) return launch_compat<K, R16, PLANES, true>(g, s);                   \
+        }                                                                                  \
+        return launch_compat<K, R16, PLANES, false>(g, s);
         SCASML_CASE(1) SCASML_CASE(2) SCASML_CASE(3) SCASML_CASE(4) SCASML_CASE(5) SCASML_CASE(6) SCASML_CASE(7) SCASML_CASE(8)
         SCASML_CASE(9) SCASML_CASE(10) SCASML_CASE(11) SCASML_CASE(12) SCASML_CASE(13) SCASML_CASE(14) SCASML_CASE(15) SCASML_CASE(16)
 #undef SCASML_CASE
@@ -742,7 +827,7 @@ extern "C" int scasml_gp_compat_pack_mfma(int32_t d, float a, const float *x_dom
     const int n_pad = (n_dom + n_bdy + 31) / 32 * 32;
     const int kp = scasml_point_stride(d);
     hipLaunchKernelGGL(gp_compat_pack_mfma_kernel, dim3((n_pad + 63) / 64), dim3(64), 0, (hipStream_t)stream, d, a, x_dom, n_dom, x_bdy, n_bdy,
-                       rv, ix, model_out, n_pad, kp);
+                       rv, ix, model_out, n_pad, kp, compat_tail_packed(d, kp) ? 1 : 0);
     return check_launch("gp_compat_pack_mfma launch");
 }
 
@@ -805,6 +890,7 @@ static int eval_compat_sites(int32_t d, float a, float sigma_eq, float mu_eq, in
     g.rows_per_site = rows_per_site;
     g.site_order = site_order;
     g.n_listed = n_listed;
+    g.tail_packed = compat_tail_packed(d, g.kp) ? 1 : 0;
     hipStream_t s = (hipStream_t)stream;
     if (round16 & 1) {
         if (round16 & 4) return fail(SCASML_ERR_ARG, "gp_eval_compat_sites: round16 bit 2 (one point plane) is the geometry mode's option, not the as-coded form's");

@@ -1,10 +1,10 @@
 #!/usr/bin/env python
 """Development: VGPR count and scratch bytes of every kernel in one csrc/*.hip (device-only compile to ISA text).
-    python tools/kernel_regs.py gp_eval_f16.hip [-DSCASML_GP_ABLATE=1]     (also leaves /tmp/<name>.s for reading)"""
+    python tools/kernel_regs.py gp_eval_f16.hip [-DSCASML_GP_ABLATE=1]     (also leaves /tmp/<name>.s, or $KERNEL_REGS_OUT, for reading)"""
 import os, re, subprocess, sys
 root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 src = os.path.join(root, "scasml_gp_amd", "csrc", sys.argv[1])
-out = "/tmp/" + sys.argv[1].replace(".hip", ".s")
+out = os.environ.get("KERNEL_REGS_OUT") or "/tmp/" + sys.argv[1].replace(".hip", ".s")     # KERNEL_REGS_OUT: callers that may run side by side
 subprocess.run([os.environ.get("HIPCC", "/opt/rocm/bin/hipcc"), "--offload-arch=gfx950", "-O3", "-std=c++17", "-ffp-contract=off", "-fno-slp-vectorize", "-w", "-S",
                 "--cuda-device-only", "-I" + os.path.join(root, "include"), "-o", out, src] + sys.argv[2:], check=True)
 t = open(out).read()
