@@ -168,52 +168,82 @@ __device__ __forceinline__ void compat_epilogue(const float *rows_lds, const f32
                                                 const CompatConsts &c, float &au, float &at, float &ad, float &al) {
     const float4 *cb = reinterpret_cast<const float4 *>(__builtin_assume_aligned(rows_lds + 4 * 8 * half, 16));   // row = (r&3) + 8 (r>>2) + 4 half
     constexpr int NQ = (BDY || GEOM == 1) ? 1 : 2;
-    float4 q[1][NQ];
+    // al reads a row's constants where they are used (its seven entries keep the other waves' reads covered, and its registers are the kernel's
+    // peak); ys and xs do a third of that work per row and then wait for the read: they fetch one row ahead (4 and 8 registers they have)
+#ifndef SCASML_COMPAT_ROW_AHEAD
+#define SCASML_COMPAT_ROW_AHEAD 1
+#endif
+    constexpr bool AHEAD = SCASML_COMPAT_ROW_AHEAD && GEOM != 0;
+    float4 q[AHEAD ? 2 : 1][NQ];
     auto fetch = [&](int r, float4 (&dst)[NQ]) {
         const int row = (r & 3) + 8 * (r >> 2);
 #pragma unroll
         for (int i = 0; i < NQ; ++i) dst[i] = cb[row * 2 + i];
     };
+    if constexpr (AHEAD) fetch(0, q[0]);
+    // The entry a row rounds ALONE (every case but the (u, div) form's ys has one: 7, 3 and 3 entries per row) is rounded together with the next
+    // row's: the even row holds its value and coefficient, the odd row rounds both with one instruction and adds the even row's term first.  In
+    // every case the lone term is the last one its row adds to its sum (the other terms of that sum are `rest`), so each sum still receives the
+    // same terms in the same order, and a float32 value rounds the same alone or in a pair: u_hat, div and dt keep their bits.  The lone
+    // entries of the full form (e6, h3, the boundary h1) are products that were rounded ONCE as long as they were alone (v_fma_mixlo_f16); they
+    // are now float32 values first, like every paired entry: `lap` can move by a float16 ulp of one term in about one entry in 8000.
+    float held_v = 0.0f, held_c = 0.0f;
+    auto lone = [&](int r, float v, float coef, float &sum, auto &&rest) {
+        if (r & 1) {
+            const Pair<R16> k(held_v, v);
+            sum = fmaf(held_c, k.lo(), sum);
+            rest();
+            sum = fmaf(coef, k.hi(), sum);
+        } else {
+            rest();
+            held_v = v;
+            held_c = coef;
+        }
+    };
+    auto none = [] {};
 #pragma unroll
     for (int r = 0; r < 16; ++r) {
-        const int cur = 0;
-        fetch(r, q[0]);             // read where used, not one row ahead: eight registers fewer (see compat_mfma_lam)
-        __builtin_amdgcn_sched_barrier(0);
+        const int cur = AHEAD ? (r & 1) : 0;
+        if constexpr (AHEAD) {
+            if (r + 1 < 16) fetch(r + 1, q[cur ^ 1]);
+        } else {
+            fetch(r, q[0]);         // read where used, not one row ahead: eight registers fewer (see compat_mfma_lam)
+        }
+        if (!(r & 1)) __builtin_amdgcn_sched_barrier(0);            // once per row pair
         const float kap = pin(__builtin_amdgcn_exp2f(lam[r]));
         if constexpr (GEOM == 0) {
             const float vsy = q[cur][0].x, vty = q[cur][0].y, c0 = q[cur][0].z;
             if constexpr (BDY && FORM == 1) {
-                const Pair<R16> k0(kap, 0.0f);
-                au = fmaf(c0, k0.lo(), au);
+                lone(r, kap, c0, au, none);
             } else {
                 const float pp = p.tx - vty, ss = p.sx - vsy;       // a r_t, a S
                 const float e1 = pin(pp * kap), e2 = pin(ss * kap);   // P[I][dt] = -P[dt][I],  P[I][div] = -P[div][I]
                 if constexpr (BDY) {                                // boundary rows: c0 only
-                    const Pair<R16> k01(kap, e1), k2(e2, 0.0f);
+                    const Pair<R16> k01(kap, e1);
                     au = fmaf(c0, k01.lo(), au);
                     if constexpr (FORM == 0) at = fmaf(-c0, k01.hi(), at);
-                    if constexpr (FORM != 1) ad = fmaf(-c0, k2.lo(), ad);
+                    lone(r, e2, -c0, ad, none);                     // FORM != 1 here
                 } else {
                     const float cL = q[cur][0].w, ct = q[cur][1].x, cS = q[cur][1].y;
                     if constexpr (FORM == 1) {
-                        const Pair<R16> k01(kap, e1), k2(e2, 0.0f);
-                        au = fmaf(cS, k2.lo(), fmaf(ct, k01.hi(), fmaf(c0, k01.lo(), au)));
+                        const Pair<R16> k01(kap, e1);
+                        lone(r, e2, cS, au, [&] { au = fmaf(ct, k01.hi(), fmaf(c0, k01.lo(), au)); });
                     } else {
                         const float e4 = pin(pp * e2);                          // a^2 r_t S kappa = -P[dt][div] = -P[div][dt]
                         const float e5 = pin(fmaf(-ss, e2, c.ad * kap));        // (a d - a^2 S^2) kappa = P[div][div]
                         if constexpr (FORM == 2) {
-                            const Pair<R16> k01(kap, e1), k24(e2, e4), k5(e5, 0.0f);
+                            const Pair<R16> k01(kap, e1), k24(e2, e4);
                             au = fmaf(cS, k24.lo(), fmaf(ct, k01.hi(), fmaf(c0, k01.lo(), au)));
-                            ad = fmaf(cS, k5.lo(), fmaf(-ct, k24.hi(), fmaf(-c0, k24.lo(), ad)));
+                            lone(r, e5, cS, ad, [&] { ad = fmaf(-ct, k24.hi(), fmaf(-c0, k24.lo(), ad)); });
                         } else {
                             const float e3 = fmaf(-pp, e1, c.a * kap);          // (a - a^2 r_t^2) kappa = P[dt][dt]
                             const float g0 = G[r];
                             const float e6 = fmaf(g0, g0 - c.c4, -c.c10) * kap; // lap_x lap_y
-                            const Pair<R16> k01(kap, e1), k23(e2, e3), k45(e4, e5), k6(e6, 0.0f);
+                            const Pair<R16> k01(kap, e1), k23(e2, e3), k45(e4, e5);
                             au = fmaf(cS, k23.lo(), fmaf(ct, k01.hi(), fmaf(c0, k01.lo(), au)));
                             at = fmaf(-cS, k45.lo(), fmaf(ct, k23.hi(), fmaf(-c0, k01.hi(), at)));
                             ad = fmaf(cS, k45.hi(), fmaf(-ct, k45.lo(), fmaf(-c0, k23.lo(), ad)));
-                            al = fmaf(cL, k6.lo(), al);
+                            lone(r, e6, cL, al, none);
                         }
                     }
                 }
@@ -223,8 +253,7 @@ __device__ __forceinline__ void compat_epilogue(const float *rows_lds, const f32
             const float g1 = G[r];
             const float f1 = pin(g1 * kap);                                     // P[I][lap]
             if constexpr (FORM == 1) {
-                const Pair<R16> k1(f1, 0.0f);
-                au = fmaf(cL, k1.lo(), au);
+                lone(r, f1, cL, au, none);
             } else {
                 const float m = fmaf(-(p.sx - vsy1), g1, p.wxb - vwy1);         // h mix1
                 const float f3 = pin(m * kap);                                  // P[div][lap]
@@ -234,10 +263,10 @@ __device__ __forceinline__ void compat_epilogue(const float *rows_lds, const f32
                     ad = fmaf(cL, k13.hi(), ad);
                 } else {
                     const float f2 = (p.tx - vay0) * f1;                        // -P[dt][lap]
-                    const Pair<R16> k12(f1, f2), k3(f3, 0.0f);
+                    const Pair<R16> k12(f1, f2);
                     au = fmaf(cL, k12.lo(), au);
                     at = fmaf(-cL, k12.hi(), at);
-                    ad = fmaf(cL, k3.lo(), ad);
+                    lone(r, f3, cL, ad, none);
                 }
             }
         } else {                                // lap_x rows (full form only)
@@ -245,15 +274,14 @@ __device__ __forceinline__ void compat_epilogue(const float *rows_lds, const f32
             const float g2 = G[r];
             const float h1 = g2 * kap;                                          // P[lap][I]
             if constexpr (BDY) {
-                const Pair<R16> k1(h1, 0.0f);
-                al = fmaf(c0, k1.lo(), al);
+                lone(r, h1, c0, al, none);
             } else {
                 const float ct = q[cur][1].x, cS = q[cur][1].y;
                 const float h2 = (p.ax0 - vty) * h1;                            // P[lap][dt]
                 const float m = fmaf(-(p.sx2 - vsy), g2, p.wxa - vwy2);         // h mix2
                 const float h3 = m * kap;                                       // -P[lap][div]
-                const Pair<R16> k12(h1, h2), k3(h3, 0.0f);
-                al = fmaf(-cS, k3.lo(), fmaf(ct, k12.hi(), fmaf(c0, k12.lo(), al)));
+                const Pair<R16> k12(h1, h2);
+                lone(r, h3, -cS, al, [&] { al = fmaf(ct, k12.hi(), fmaf(c0, k12.lo(), al)); });
             }
         }
     }
@@ -336,22 +364,35 @@ __device__ __forceinline__ void compat_epilogue_fact(const float *rows_lds, cons
 // Stage block, in floats (scasml_gp_compat_pack_mfma): KS*256 planes | 256 Q fragment | 256 row constants (32 x 8) = (KS + 2) KiB
 constexpr int kStageTail = 256 + 256;
 
+#ifndef SCASML_COMPAT_NSLOT
+#define SCASML_COMPAT_NSLOT 3
+#endif
+// As coded, the two Q fragments of a wave's points (B operands of the G product, each read once per stage) are parked in LDS behind the ring, one
+// region per wave, instead of eight registers held through the sweep: 2 x 64 lanes x 16 B per wave, 8 KiB per workgroup.  The geometry mode has
+// the registers and keeps them there (at one plane and KS = 9 the region would cost it a workgroup per CU).
+constexpr int kQParkWave = 2 * 64 * 4;      // floats per wave
+// LDS of a workgroup, in floats: the kernels' one static array, and what the launch counts workgroups per CU with
+template <int KS, bool R16>
+constexpr int compat_lds_floats() {
+    return SCASML_COMPAT_NSLOT * (KS * 256 + kStageTail) + (R16 ? 4 * kQParkWave : 0);
+}
+
 // The body of both kernels below: PACK = the tail-packed column map (compat_tail_packed).
 template <int KS, bool R16, int PLANES, bool PACK>
 __device__ __forceinline__ void compat_mfma_sweep(const GpCompatArgs g) {
     static_assert(PLANES == 2 || !R16, "the as-coded form keeps both point planes");
     // three slots: stage s is read while s + 1 has landed or lands and s + 2 is issued into the slot stage s - 1 was read from, which
     // every wave left before the barrier that ended step s - 1
-#ifndef SCASML_COMPAT_NSLOT
-#define SCASML_COMPAT_NSLOT 3
-#endif
     constexpr int WPB = 4, NSLOT = SCASML_COMPAT_NSLOT, AHEAD = 2;
     constexpr int STAGE = KS * 256 + kStageTail;       // floats per LDS slot
     constexpr int NCHUNK = STAGE / 256;
     constexpr int CLO = NCHUNK / WPB, CREM = NCHUNK % WPB;
-    extern __shared__ __attribute__((aligned(16))) float lds[];
+    constexpr bool QLDS = R16;                         // Q fragments parked in LDS (compat_lds_floats)
+    __shared__ __attribute__((aligned(16))) float lds[compat_lds_floats<KS, R16>()];
     const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-    const int col = lane & 31, half = lane >> 5;
+    const int col = lane & 31;
+    const int half = (int)__builtin_amdgcn_mbcnt_lo(0x80000000u, 0u);     // lane >> 5 as ONE instruction without inputs: formed again where it is used, not kept
+                                                                          // through the sweep (the one-plane geometry instance at KS = 8 spilled it)
     const int64_t blk = blockIdx.x;
     int64_t p0 = (blk * WPB + wv) * 32;
     const int n_tiles = g.n_pad / 32;
@@ -414,8 +455,9 @@ __device__ __forceinline__ void compat_mfma_sweep(const GpCompatArgs g) {
     const int n_stages = nb0 * GD + (n_tiles - nb0) * GB;
 
     const int wvs = __builtin_amdgcn_readfirstlane(wv);
+    int lane_s = lane, half_s = half;       // lane and half-wave as the sweep reads them (one plane: formed again where each form's sweep begins)
     const bool extra = wvs < CREM;
-    const uint32_t lds_base = __builtin_amdgcn_readfirstlane((uint32_t)(uintptr_t)lds);
+    const uint32_t lds_base = (uint32_t)(uintptr_t)lds;
     // stage s of this form -> its block of the model: (tile, geometry)
     auto stage_src = [&](int s) -> const float * {
         int tile, geom;
@@ -432,7 +474,7 @@ __device__ __forceinline__ void compat_mfma_sweep(const GpCompatArgs g) {
     auto stage = [&](int s) {
         const uint32_t dst = lds_base + (uint32_t)((s % NSLOT) * STAGE) * 4u;
         const float *src = stage_src(s);
-        auto chunk = [&](int c) { glds16_asm(src + c * 256, (uint32_t)lane * 16u, dst + (uint32_t)c * 1024u); };
+        auto chunk = [&](int c) { glds16_asm(src + c * 256, (uint32_t)lane_s * 16u, dst + (uint32_t)c * 1024u); };
 #pragma unroll
         for (int i = 0; i < CLO; ++i) chunk(wvs + i * WPB);
         if (CREM && extra) chunk(wvs + CLO * WPB);
@@ -461,6 +503,9 @@ __device__ __forceinline__ void compat_mfma_sweep(const GpCompatArgs g) {
     float acc0 = 0.0f;          // PLANES == 1: the low part of the |x|^2 column, which the dropped plane would have carried
     CompatPoint pt;
     Frag qa[1], qb[1];          // B fragments of the Q products: components i_j + 1 (al, xs) and i_j (ys)
+    // their home when parked: written here by the wave that reads them, so program order and the compiler's own lgkmcnt are all the
+    // synchronisation there is; no other wave and no LDS-DMA touches the region
+    float4 *qpark = reinterpret_cast<float4 *>(lds + NSLOT * STAGE) + wvs * (kQParkWave / 4);
     {
         int64_t row = p0 + col;
         if (row >= g.n_inf) row = g.n_inf - 1;   // shadow rows, never stored
@@ -557,6 +602,9 @@ __device__ __forceinline__ void compat_mfma_sweep(const GpCompatArgs g) {
         }
         pt.wxa = 2.0f * ha2 * sa;
         pt.wxb = 2.0f * ha2 * sb;
+        // one plane: ax0, sx2 and wxa are read by the full form only, and the compiler moved their loads to that form's sweep and carried x_0 and
+        // the row pointer there through scratch: formed here
+        if constexpr (PLANES == 1) asm volatile("" : "+v"(pt.ax0), "+v"(pt.sx2), "+v"(pt.wxa));
         // Q fragment, K = 16: half 0 = (u_0..4 high parts, PX_h, PX_l, 1), half 1 = (u_0..4 low parts, 1, 0, 0)
         auto qfrag = [&](const float (&u)[kHutch], float px, Frag &f) {
             auto hi = [](float v) { return (float)(_Float16)v; };
@@ -575,12 +623,26 @@ __device__ __forceinline__ void compat_mfma_sweep(const GpCompatArgs g) {
         const float c5ah = (float)kHutch * g.a * hh;
         qfrag(ua, fmaf(ha2, na, -c5ah), qa[0]);
         qfrag(ub, fmaf(ha2, nb, -c5ah), qb[0]);
+        if constexpr (QLDS) {
+            qpark[lane] = qa[0].f;
+            qpark[64 + lane] = qb[0].f;
+        }
     }
+    // One plane, four (three) workgroups per CU: what is formed from the lane in front of the prologue and read in the sweep or at the store
+    // (fragment, row-constant and LDS-DMA offsets, the output row) was spilled between them.  The lane index is two instructions without inputs:
+    // each form's sweep and the store form it again, so nothing derived from it lives from one to the next (the operand only ties the place).
+    auto late_lane = [](float after) {
+        int x;
+        asm volatile("v_mbcnt_lo_u32_b32 %0, -1, 0\n\tv_mbcnt_hi_u32_b32 %0, -1, %0" : "=v"(x) : "v"(after));
+        return x;
+    };
+    // uniform values computed on the vector ALU: back to scalar registers
+    auto uni = [](float v) { return __builtin_bit_cast(float, __builtin_amdgcn_readfirstlane(__builtin_bit_cast(int, v))); };
     CompatConsts cc;
     cc.a = g.a;
-    cc.ad = g.a * (float)g.d;
-    cc.c4 = 4.0f * g.a * hh;
-    cc.c10 = 10.0f * g.a * g.a * hh * hh;
+    cc.ad = uni(g.a * (float)g.d);
+    cc.c4 = uni(4.0f * g.a * hh);
+    cc.c10 = uni(10.0f * g.a * g.a * hh * hh);
     float au = 0.0f, at = 0.0f, ad = 0.0f, al = 0.0f;
     f32x16 acc, accG;
     uint32_t region;
@@ -595,18 +657,20 @@ __device__ __forceinline__ void compat_mfma_sweep(const GpCompatArgs g) {
         if (s_now + AHEAD < n_stages) stage(s_now + AHEAD);
         const float *base = lds + slot * STAGE;
         if (region & 1) {
-            compat_mfma_lam<KS, PLANES, PACK>(reinterpret_cast<const float4 *>(base), xb, acc, lane, acc0);
+            compat_mfma_lam<KS, PLANES, PACK>(reinterpret_cast<const float4 *>(base), xb, acc, lane_s, acc0);
             if constexpr (NEEDG) {
                 Frag aq;
-                aq.f = reinterpret_cast<const float4 *>(base + KS * 256)[lane];
+                aq.f = reinterpret_cast<const float4 *>(base + KS * 256)[lane_s];
 #pragma unroll
                 for (int r = 0; r < 16; ++r) accG[r] = 0.0f;
-                accG = __builtin_amdgcn_mfma_f32_32x32x16_f16(aq.h, GEOM == 1 ? qb[0].h : qa[0].h, accG, 0, 0, 0);
+                Frag bq = GEOM == 1 ? qb[0] : qa[0];
+                if constexpr (QLDS) bq.f = qpark[(GEOM == 1 ? 64 : 0) + lane];
+                accG = __builtin_amdgcn_mfma_f32_32x32x16_f16(aq.h, bq.h, accG, 0, 0, 0);
             }
         }
         if (region & 2) {
-            if constexpr (R16) compat_epilogue<GEOM, FORM, BDY, true>(base + (KS + 1) * 256, acc, accG, half, pt, cc, au, at, ad, al);
-            else compat_epilogue_fact<GEOM, FORM, BDY>(base + (KS + 1) * 256, acc, accG, half, pt, cc, au, at, ad, al);
+            if constexpr (R16) compat_epilogue<GEOM, FORM, BDY, true>(base + (KS + 1) * 256, acc, accG, half_s, pt, cc, au, at, ad, al);
+            else compat_epilogue_fact<GEOM, FORM, BDY>(base + (KS + 1) * 256, acc, accG, half_s, pt, cc, au, at, ad, al);
         }
         rendezvous(s_now + AHEAD < n_stages);
         ++s_now;
@@ -616,6 +680,10 @@ __device__ __forceinline__ void compat_mfma_sweep(const GpCompatArgs g) {
     using I2 = std::integral_constant<int, 2>;
     auto sweep = [&](auto form_c) {
         constexpr int FORM = decltype(form_c)::value;
+        if constexpr (PLANES == 1) {
+            lane_s = late_lane(au);
+            half_s = lane_s >> 5;
+        }
         for (int jt = 0; jt < nb0; ++jt) {
             step(I0{}, form_c, std::false_type{});
             step(I1{}, form_c, std::false_type{});
@@ -631,18 +699,37 @@ __device__ __forceinline__ void compat_mfma_sweep(const GpCompatArgs g) {
     else if (form == 1) sweep(I1{});
     else sweep(I0{});
 
-    float u = au + __shfl_xor(au, 32);
-    const float dt = at + __shfl_xor(at, 32);
-    const float dv = ad + __shfl_xor(ad, 32);
-    const float lp = al + __shfl_xor(al, 32);
+    // the other half-wave's sums; one plane: through an address formed here, not the prologue's (which was spilled to get here)
+    auto other_half = [&](float v) {
+        if constexpr (PLANES == 1) {
+            const int peer = (late_lane(v) ^ 32) << 2;
+            return __builtin_bit_cast(float, __builtin_amdgcn_ds_bpermute(peer, __builtin_bit_cast(int, v)));
+        } else {
+            return __shfl_xor(v, 32);
+        }
+    };
+    float u = au + other_half(au);
+    const float dt = at + other_half(at);
+    const float dv = ad + other_half(ad);
+    const float lp = al + other_half(al);
     // tail-packed as-coded form: the output row is formed again from the scalar p0, not kept in two registers through the sweep (KS = 7 sits at
     // 128 registers and spilled exactly this pair); the other instances allocate better with the prologue's value kept
     int col_out = col;
     if constexpr (R16) asm volatile("" : "+v"(col_out));
+    int half_out = half;
+    float fd = (float)g.d;
+    if constexpr (PLANES == 1) {
+        const int l = late_lane(u);
+        col_out = l & 31;
+        half_out = l >> 5;
+        int d_late = g.d;
+        asm volatile("" : "+s"(d_late));          // (float)d of the prologue's h = d / 5 is not kept either
+        fd = (float)d_late;
+    }
     const int64_t row = p0 + col_out;
-    if (half == 0 && row < g.n_inf) {
+    if (half_out == 0 && row < g.n_inf) {
         if (g.round_out) u = (float)(_Float16)u;                               // predict(...).astype(float16), models/GP.py:671
-        float eps = dt + g.mu * dv + 0.5f * g.sigma * g.sigma * lp + eq_f<float>(g.eq_id, u, g.sigma * dv, g.sigma, (float)g.d);   // :767-768
+        float eps = dt + g.mu * dv + 0.5f * g.sigma * g.sigma * lp + eq_f<float>(g.eq_id, u, g.sigma * dv, g.sigma, fd);   // :767-768
         if (g.round_out) eps = (float)(_Float16)eps;                           // :769
         g.out4[row] = make_float4(u, dv, eps, dt);
         if (g.lap) g.lap[row] = lp;
@@ -762,22 +849,18 @@ static int launch_compat(const GpCompatArgs &g, hipStream_t s) {
     // constants and temporaries.  A packed tail frees the four of the last low-plane fragment; the estimate (and with it BPC) stays the long-tail
     // one for both maps: as coded, KS = 7 is 128 registers without scratch in either (tests/test_kpack_registers.py)
     constexpr int REGS = 4 * PLANES * KS + (R16 ? 72 : 90);
-    constexpr size_t lds_bytes = SCASML_COMPAT_NSLOT * (size_t)(KS * 256 + kStageTail) * sizeof(float);
+    constexpr size_t lds_bytes = compat_lds_floats<KS, R16>() * sizeof(float);       // static: the code object's metadata states it
     constexpr int BPC_REGS = REGS <= 128 ? 4 : (REGS <= 164 ? 3 : 2), BPC_LDS = (int)(160 * 1024 / lds_bytes);
     constexpr int BPC = BPC_REGS < BPC_LDS ? BPC_REGS : BPC_LDS;
     const int64_t waves = g.site_order ? (int64_t)g.n_listed * (g.rows_per_site >> 5) : (g.n_inf + 31) / 32;
     const int64_t blocks = (waves + 3) / 4;
     if (blocks == 0) return 0;
     if (blocks > 0x7FFFFFFF) return fail(SCASML_ERR_UNSUPPORTED, "gp_eval_compat_sites: too many points");
-    static_assert(lds_bytes * BPC <= 160 * 1024, "LDS slots exceed 160 KiB");
+    static_assert(lds_bytes * BPC <= 160 * 1024 && lds_bytes <= 64 * 1024, "LDS slots exceed 160 KiB per CU or 64 KiB per workgroup");
     void (*kern)(const GpCompatArgs) = gp_eval_compat_mfma_kernel<KS, BPC, R16, PLANES>;
     if constexpr (PACK) kern = gp_eval_compat_mfma_tail_kernel<KS, BPC, R16, PLANES>;
     static_assert(PLANES == 2 || !PACK, "one plane: one kernel for both column maps");
-    if (lds_bytes > 64 * 1024) {
-        if (hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes) != hipSuccess)
-            return fail(SCASML_ERR_HIP, "gp_eval_compat_sites: cannot reserve %zu bytes of LDS", lds_bytes);
-    }
-    hipLaunchKernelGGL(kern, dim3((unsigned)blocks), dim3(256), lds_bytes, s, g);
+    hipLaunchKernelGGL(kern, dim3((unsigned)blocks), dim3(256), 0, s, g);
     return check_launch("gp_eval_compat_sites launch");
 }
 

@@ -1,5 +1,5 @@
 #!/usr/bin/env python
-"""Development: VGPR count and scratch bytes of every kernel in one csrc/*.hip (device-only compile to ISA text).
+"""Development: VGPR count, scratch bytes, static LDS bytes and spilled dwords of every kernel in one csrc/*.hip (device-only compile to ISA text).
     python tools/kernel_regs.py gp_eval_f16.hip [-DSCASML_GP_ABLATE=1]     (also leaves /tmp/<name>.s, or $KERNEL_REGS_OUT, for reading)"""
 import os, re, subprocess, sys
 root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -20,7 +20,9 @@ for line in t.split("\n"):
         loop = "Loop" in line
     elif cur and loop and line.strip().startswith("scratch_"):
         in_loop[cur] = in_loop.get(cur, 0) + 1
-for m in re.finditer(r'\.name:\s+(\S+)\n(?:.*\n)*?\s+\.private_segment_fixed_size:\s+(\d+)\n(?:.*\n)*?\s+\.vgpr_count:\s+(\d+)', t):
-    name = subprocess.run(["c++filt", m.group(1)], capture_output=True, text=True).stdout.strip()
-    print("%-90s scratch %4s  vgpr %3s%s" % (name[:90], m.group(2), m.group(3),
-                                             "   !! %d scratch ops inside loops" % in_loop[m.group(1)] if m.group(1) in in_loop else ""))
+# lds: the STATIC LDS of the kernel (dynamic LDS is the launch's and not in the metadata); spill: dwords of VGPRs the allocator parked in scratch
+for m in re.finditer(r'\.group_segment_fixed_size:\s+(\d+)\n(?:.*\n)*?\s+\.name:\s+(\S+)\n(?:.*\n)*?\s+\.private_segment_fixed_size:\s+(\d+)\n(?:.*\n)*?'
+                     r'\s+\.vgpr_count:\s+(\d+)\n(?:.*\n)*?\s+\.vgpr_spill_count:\s+(\d+)', t):
+    name = subprocess.run(["c++filt", m.group(2)], capture_output=True, text=True).stdout.strip()
+    print("%-90s scratch %4s  vgpr %3s  lds %6s  spill %3s%s" % (name[:90], m.group(3), m.group(4), m.group(1), m.group(5),
+                                                             "   !! %d scratch ops inside loops" % in_loop[m.group(2)] if m.group(2) in in_loop else ""))
