@@ -128,28 +128,38 @@ class GP(object):
         return out
 
     # ------------------------------------------------------------------ device helpers
-    def _points_device(self, x):
-        """(n, d+1) numpy / torch -> ((n, kp) float32 CUDA rows (X, t, zero pad), was_numpy, host bound, float16 rows).  The largest
-        |coordinate| of a host array is taken on the host, so that the evaluation need not read it back from the device (None for device
-        tensors); ``float16 rows`` says the caller's array was float16 -- numpy or torch alike -- i.e. rows on which the reference's kernels
-        are float16 arithmetic (f16_graph).  Both travel as return values: nothing about one call is parked on the instance."""
+    def _check_rows(self, x):
+        if x.dim() != 2 or x.shape[1] != self.d + 1:
+            raise ValueError("points must have shape (n, %d), got %s" % (self.d + 1, tuple(x.shape)))
+
+    def _rows_device(self, x, flat=False):
+        """(n, d+1) numpy / torch -> (float32 contiguous CUDA rows, was_numpy, float16 rows): the one intake of a caller's points.  ``float16
+        rows`` says the caller's array was float16 -- numpy or torch alike -- i.e. rows on which the reference's kernels are float16 arithmetic
+        (f16_graph).  flat (the cross-kernel builders): any array of n (d+1) entries is taken as n rows."""
         torch = _lib.require_gpu()
         was_numpy = not isinstance(x, torch.Tensor)
+        f16_rows = (np.asarray(x).dtype == np.float16) if was_numpy else x.dtype == torch.float16
+        xi = torch.from_numpy(np.ascontiguousarray(np.asarray(x), dtype=np.float32)) if was_numpy else x
+        xi = xi.to(device="cuda", dtype=torch.float32).contiguous()
+        if flat:
+            xi = xi.reshape(-1, self.d + 1)
+        self._check_rows(xi)
+        return xi, was_numpy, bool(f16_rows)
+
+    def _points_device(self, x):
+        """(n, d+1) numpy / torch -> ((n, kp) float32 CUDA rows (X, t, zero pad), was_numpy, host bound, float16 rows).  The largest
+        |coordinate| of a host array is taken on the host, from its float32 values, so that the evaluation need not read it back from the
+        device (None for device tensors).  Both travel as return values: nothing about one call is parked on the instance."""
+        torch = _lib.require_gpu()
+        xt, was_numpy, f16_rows = self._rows_device(x)
         bound = None
         if was_numpy:
-            f16_rows = np.asarray(x).dtype == np.float16
-            arr = np.ascontiguousarray(np.asarray(x), dtype=np.float32)
+            arr = np.asarray(x, dtype=np.float32)
             bound = float(np.abs(arr).max()) if arr.size else 0.0
-            xt = torch.from_numpy(arr).cuda()
-        else:
-            f16_rows = x.dtype == torch.float16
-            xt = x.to(device="cuda", dtype=torch.float32)
-        if xt.dim() != 2 or xt.shape[1] != self.d + 1:
-            raise ValueError("points must have shape (n, %d), got %s" % (self.d + 1, tuple(xt.shape)))
         kp = int(_lib.load().scasml_point_stride(self.d))
         pts = torch.zeros((xt.shape[0], kp), dtype=torch.float32, device="cuda")
         pts[:, :self.d + 1] = xt
-        return pts, was_numpy, bound, bool(f16_rows)
+        return pts, was_numpy, bound, f16_rows
 
     @property
     def a(self):
@@ -172,20 +182,29 @@ class GP(object):
         return self.compat_eval == "mfma" and not self._f16_graph_rows(f16_rows)
 
     def _gram_bits(self, x_dom, x_bdy, f16_rows=True):
-        """round16 of the as-coded Gram, Gram rows and cross rows: entries rounded; f16_graph on float16 rows and collocation points: float16 ops."""
+        """round16 of the as-coded Gram, Gram rows and cross rows: entries rounded; f16_graph on float16 rows and collocation points: float16 ops.
+        The documented operators round nothing: 0."""
+        if self.compat is None:
+            return 0
         graph = self.f16_graph and f16_rows and _f16_exact(x_dom, x_bdy)
         return _lib.ROUND16_ENTRIES | (_lib.ROUND16_F16_OPS | self._f16_extra if graph else 0)
 
+    def _require_trained(self):
+        if self.right_vector is None:
+            raise _lib.ScasmlError("GP is not trained: call GPsolver(x_domain, x_boundary) first")
+
+    @property
+    def _idx_ptr(self):
+        """The Hutchinson index set as the library takes it: its pointer for the as-coded surrogate, None for the documented operators."""
+        return self.laplacian_idx.ctypes.data_as(C.c_void_p) if self.compat == "reference" else None
+
     def _f64_model(self):
         """The fit as the as-coded float64 kernels take it: collocation columns, n_dom, n_bdy, ldc, right_vector, Hutchinson indices."""
-        if self.right_vector is None:
-            raise _lib.ScasmlError("GP is not trained: call GPsolver(x_domain, x_boundary) first")
-        return (_lib.ptr(self._colloc_t), self.N_domain, self.N_boundary, self.N_domain + self.N_boundary, _lib.ptr(self._rv_dev),
-                self.laplacian_idx.ctypes.data_as(C.c_void_p))
+        self._require_trained()
+        return (_lib.ptr(self._colloc_t), self.N_domain, self.N_boundary, self.N_domain + self.N_boundary, _lib.ptr(self._rv_dev), self._idx_ptr)
 
     def _device_model(self, x_bound=0.0):
-        if self.right_vector is None:
-            raise _lib.ScasmlError("GP is not trained: call GPsolver(x_domain, x_boundary) first")
+        self._require_trained()
         m = _lib.GpModel()
         m.x_bound = float(x_bound)
         m.d, m.n_dom, m.n_bdy, m.n_pad = self.d, self.N_domain, self.N_boundary, self._n_pad
@@ -217,8 +236,7 @@ class GP(object):
         sites only; f16_rows: the caller's rows were float16).  As coded: the matrix-core kernel where the rows may take fp16 planes
         (_fp16_planes) within their range, else the float64 kernel; the documented operators: the split demoted out of that range."""
         lib = _lib.load()
-        if self.right_vector is None:
-            raise _lib.ScasmlError("GP is not trained: call GPsolver(x_domain, x_boundary) first")
+        self._require_trained()
         if self.compat is None:
             model = self._device_model(x_bound)
             if kinds is None:
@@ -229,8 +247,7 @@ class GP(object):
             return
         r16 = int(self.eval_round16)
         if self._fp16_planes(f16_rows) and self._compat_model is not None and self._fp16_in_range(x_bound):
-            args = (_lib.ptr(self._compat_model), self.N_domain, self.N_boundary, self.laplacian_idx.ctypes.data_as(C.c_void_p), r16, float(x_bound),
-                    _lib.ptr(pts), n_rows)
+            args = (_lib.ptr(self._compat_model), self.N_domain, self.N_boundary, self._idx_ptr, r16, float(x_bound), _lib.ptr(pts), n_rows)
             if order is not None and kinds is not None and rows_per_site % 32 == 0 and n_rows % rows_per_site == 0:
                 name, args = "gp_eval_compat_site_list", args + (rows_per_site, _lib.ptr(kinds), _lib.ptr(order), int(order.numel()))
             else:
@@ -248,29 +265,56 @@ class GP(object):
         return self._eval_device(pts, hb, f16)[:, 0:1]
 
     # ------------------------------------------------------------------ training
+    def _set_collocation(self, x_t_domain, x_t_boundary):
+        """Take the collocation sets: host copies, new float32 device tensors (a cached factor belongs to THESE tensors, _L_made_for), sizes."""
+        torch = _lib.require_gpu()
+        self.x_t_domain, self.x_t_boundary = np.asarray(x_t_domain), np.asarray(x_t_boundary)
+        self._xd = torch.from_numpy(np.ascontiguousarray(self.x_t_domain, dtype=np.float32)).cuda()
+        self._xb = torch.from_numpy(np.ascontiguousarray(self.x_t_boundary, dtype=np.float32)).cuda()
+        self.N_domain, self.N_boundary = self._xd.shape[0], self._xb.shape[0]
+        self.phi_dim = 4 * self.N_domain + self.N_boundary
+
+    @staticmethod
+    def _identity_padded(A):
+        """A copy of the square device matrix A in the top left of an identity, its order rounded up to 32 (what the blocked FP64 kernels take)."""
+        torch = _lib.require_gpu()
+        n = A.shape[0]
+        Ap = torch.eye(_round_up(n, 32), dtype=torch.float64, device="cuda")
+        Ap[:n, :n] = A
+        return Ap
+
+    def _factor(self, Ap, nugget, what, stage=None):
+        """Cholesky of Ap + nugget I in place (Ap identity-padded, lower triangle read); returns the pivot info, 0 when positive definite.
+        stage: the name under which kernel_phi_phi has the call timed."""
+        torch = _lib.require_gpu()
+        info = torch.zeros(1, dtype=torch.int32, device="cuda")
+        call = lambda: _lib.check(_lib.load().scasml_cholesky(_lib.ptr(Ap), Ap.shape[0], float(nugget), _lib.ptr(info), _lib.stream_ptr()), what)
+        if stage:
+            self._stage(stage, call)
+        else:
+            call()
+        return int(info.item())
+
+    def _factor_padded(self, A, nugget, what, stage=None):
+        """(factor, pivot info) of A + nugget I, factored in an identity-padded copy of A."""
+        Ap = self._identity_padded(A)
+        return Ap, self._factor(Ap, nugget, what, stage)
+
     def kernel_phi_phi(self, x_t_domain, x_t_boundary):
         '''K(phi,phi) + nugget*I as a CUDA float64 tensor; also factors it (models/GP.py:182-268).'''
         torch = _lib.require_gpu()
         lib = _lib.load()
-        xd = torch.from_numpy(np.ascontiguousarray(np.asarray(x_t_domain), dtype=np.float32)).cuda()
-        xb = torch.from_numpy(np.ascontiguousarray(np.asarray(x_t_boundary), dtype=np.float32)).cuda()
-        self.N_domain, self.N_boundary = xd.shape[0], xb.shape[0]
-        self.phi_dim = M = 4 * self.N_domain + self.N_boundary
-        self.x_t_domain, self.x_t_boundary = np.asarray(x_t_domain), np.asarray(x_t_boundary)
-        self._xd, self._xb = xd, xb
+        self._set_collocation(x_t_domain, x_t_boundary)
+        xd, xb, M = self._xd, self._xb, self.phi_dim
         s = _lib.stream_ptr()
         K = torch.empty((M, M), dtype=torch.float64, device="cuda")
         as_coded = self.compat == "reference"
         name = "gp_gram_compat" if as_coded else "gp_gram"
-        compat_args = (self.laplacian_idx.ctypes.data_as(C.c_void_p), self._gram_bits(xd, xb)) if as_coded else ()
+        compat_args = (self._idx_ptr, self._gram_bits(xd, xb)) if as_coded else ()
         self._stage("gram", lambda: _lib.check(getattr(lib, "scasml_" + name)(
             self.d, self.a, _lib.ptr(xd), self.N_domain, _lib.ptr(xb), self.N_boundary, *compat_args, _lib.ptr(K), s), name))
-        Mp = _round_up(M, 32)
-        L = torch.eye(Mp, dtype=torch.float64, device="cuda")
-        L[:M, :M] = K
-        info = torch.zeros(1, dtype=torch.int32, device="cuda")
-        self._stage("cholesky", lambda: _lib.check(lib.scasml_cholesky(_lib.ptr(L), Mp, float(self.nugget), _lib.ptr(info), s), "cholesky"))
-        if int(info.item()) != 0 or bool(torch.isnan(L).any()):
+        L, info = self._factor_padded(K, self.nugget, "cholesky", stage="cholesky")
+        if info != 0 or bool(torch.isnan(L).any()):
             raise ValueError("Cholesky decomposition resulted in NaN values.")        # models/GP.py:264-265
         self._L_pad = L
         self._L_made_for = (xd, xb, self.nugget)           # predict_variance: the factor belongs to these collocation tensors
@@ -321,15 +365,12 @@ class GP(object):
             Lg = torch.as_tensor(np.asarray(L.detach().cpu() if isinstance(L, torch.Tensor) else L, dtype=np.float64), device="cuda")
             if Lg.shape != (M, M):
                 raise ValueError("L has shape %s, expected (%d, %d)" % (tuple(Lg.shape), M, M))
-            Lp = torch.eye(_round_up(M, 32), dtype=torch.float64, device="cuda")
             if bool((torch.triu(Lg, 1) != 0).any()):          # a general factor (the reference's own is U sqrt(S)): the Cholesky factor of L L^T
-                Lp[:M, :M] = Lg @ Lg.T
-                info = torch.zeros(1, dtype=torch.int32, device="cuda")
-                _lib.check(lib.scasml_cholesky(_lib.ptr(Lp), Lp.shape[0], 0.0, _lib.ptr(info), s), "cholesky(L L^T)")
-                if int(info.item()) != 0:
+                Lp, info = self._factor_padded(Lg @ Lg.T, 0.0, "cholesky(L L^T)")
+                if info != 0:
                     raise ValueError("L L^T is not positive definite")
             else:
-                Lp[:M, :M] = Lg
+                Lp = self._identity_padded(Lg)
         Mp = Lp.shape[0]
         b = torch.zeros((Mp, 1), dtype=torch.float64, device="cuda")
         _lib.check(lib.scasml_gp_newton_b(int(self.equation.eq_id), int(self.d), float(self.equation.sigma()), float(self.equation.mu()), _lib.ptr(sol_d),
@@ -344,10 +385,8 @@ class GP(object):
         torch = _lib.require_gpu()
         lib = _lib.load()
         npad = Hp.shape[0]
-        info = torch.zeros(1, dtype=torch.int32, device="cuda")
         s = _lib.stream_ptr()
-        _lib.check(lib.scasml_cholesky(_lib.ptr(Hp), npad, float(damping), _lib.ptr(info), s), "cholesky(newton)")
-        if int(info.item()) != 0:
+        if self._factor(Hp, damping, "cholesky(newton)") != 0:
             return None
         b = torch.zeros((npad, 1), dtype=torch.float64, device="cuda")
         b[:n, 0] = rhs
@@ -416,8 +455,7 @@ class GP(object):
             # z4 = time_der_rep(sol).astype(float16) (:719), right_vector = solve(float16(K_p), z) (:268, 599): a second
             # factorisation, of the rounded matrix (still positive definite: rounding moves only the diagonal, by < nugget)
             _lib.check(lib.scasml_round16(C.c_void_p(b.data_ptr() + 8 * (2 * N + Nb)), N, s), "round16")
-            Lp = torch.eye(Mp, dtype=torch.float64, device="cuda")
-            Lp[:M, :M] = Kp
+            Lp = self._identity_padded(Kp)
             del Kp
             rv = self._chol_solve_padded(Lp, b, M, 0.0)
             del Lp
@@ -449,8 +487,8 @@ class GP(object):
             if self._colloc_is_f16:
                 self._compat_model = torch.empty((int(lib.scasml_gp_compat_model_floats(self.d, self._n_pad)),), dtype=torch.float32, device="cuda")
                 _lib.check(lib.scasml_gp_compat_pack_mfma(self.d, self.a, _lib.ptr(self._xd), self.N_domain, _lib.ptr(self._xb),
-                                                          self.N_boundary, _lib.ptr(self._rv_dev), self.laplacian_idx.ctypes.data_as(C.c_void_p),
-                                                          _lib.ptr(self._compat_model), _lib.stream_ptr()), "gp_compat_pack_mfma")
+                                                          self.N_boundary, _lib.ptr(self._rv_dev), self._idx_ptr, _lib.ptr(self._compat_model),
+                                                          _lib.stream_ptr()), "gp_compat_pack_mfma")
         else:
             kp = int(lib.scasml_point_stride(self.d))
             self._colloc = torch.empty((self._n_pad, kp), dtype=torch.float32, device="cuda")
@@ -466,11 +504,7 @@ class GP(object):
     def load_right_vector(self, x_t_domain, x_t_boundary, right_vector):
         '''Install a trained state (collocation points + right_vector) without running GPsolver.'''
         torch = _lib.require_gpu()
-        self.x_t_domain, self.x_t_boundary = np.asarray(x_t_domain), np.asarray(x_t_boundary)
-        self._xd = torch.from_numpy(np.ascontiguousarray(self.x_t_domain, dtype=np.float32)).cuda()
-        self._xb = torch.from_numpy(np.ascontiguousarray(self.x_t_boundary, dtype=np.float32)).cuda()
-        self.N_domain, self.N_boundary = self._xd.shape[0], self._xb.shape[0]
-        self.phi_dim = 4 * self.N_domain + self.N_boundary
+        self._set_collocation(x_t_domain, x_t_boundary)
         rv = np.asarray(right_vector, dtype=np.float64).reshape(-1)
         if rv.size != self.phi_dim:
             raise ValueError("right_vector has %d entries, expected %d" % (rv.size, self.phi_dim))
@@ -525,6 +559,7 @@ class GP(object):
     # posterior variance (no counterpart in models/GP.py, which keeps only right_vector): var(x) = kappa(x, x) - |L^-1 K(x, phi)|^2 with the factor
     # L of K(phi, phi) + nugget I that kernel_phi_phi leaves on the device
     variance_buffer_bytes = 1 << 30     # cap of the (points x Mp) float64 row buffer predict_variance works in; n is walked in chunks under it
+    cross_rows_per_call = 65535 * 16    # the most rows scasml_gp_cross_rows takes in one call; _cross_rows walks longer sets under it
 
     def _variance_factor(self):
         """The padded float64 factor of K(phi, phi) + nugget I for the collocation points this GP holds.  kernel_phi_phi / GPsolver leave it;
@@ -553,27 +588,15 @@ class GP(object):
         Needs the factor of K(phi, phi) + nugget I: GPsolver / kernel_phi_phi leave it; after load_state_dict / load / load_right_vector the first
         call rebuilds it (one Gram + one Cholesky factorisation) and keeps it.  state_dict does not carry it.'''
         torch = _lib.require_gpu()
-        lib = _lib.load()
         L = self._variance_factor()
-        was_numpy = not isinstance(x_t_infer, torch.Tensor)
-        f16_rows = (np.asarray(x_t_infer).dtype == np.float16) if was_numpy else x_t_infer.dtype == torch.float16
-        xi = x_t_infer if not was_numpy else torch.from_numpy(np.ascontiguousarray(np.asarray(x_t_infer), dtype=np.float32))
-        xi = xi.to(device="cuda", dtype=torch.float32).contiguous()
-        if xi.dim() != 2 or xi.shape[1] != self.d + 1:
-            raise ValueError("points must have shape (n, %d), got %s" % (self.d + 1, tuple(xi.shape)))
+        xi, was_numpy, f16_rows = self._rows_device(x_t_infer)
         n, Mp = xi.shape[0], L.shape[0]
-        as_coded = self.compat == "reference"
-        r16 = self._gram_bits(self._xd, self._xb, f16_rows) if as_coded else 0
+        r16 = self._gram_bits(self._xd, self._xb, f16_rows)
         var = torch.empty((n, 1), dtype=torch.float64, device="cuda")
-        chunk = int(max(1, min(self.variance_buffer_bytes // (8 * Mp), 65535 * 16, n)))
-        rows = torch.zeros((chunk, Mp), dtype=torch.float64, device="cuda") if n else None   # columns M .. Mp stay zero (L is identity there)
-        s = _lib.stream_ptr()
+        chunk = int(max(1, min(self.variance_buffer_bytes // (8 * Mp), n)))
+        rows = torch.zeros((chunk, Mp), dtype=torch.float64, device="cuda") if n else None
         for lo in range(0, n, chunk):
-            m = min(chunk, n - lo)
-            _lib.check(lib.scasml_gp_cross_rows(self.d, self.a, _lib.ptr(self._xd), self.N_domain, _lib.ptr(self._xb) if self.N_boundary else None,
-                                                self.N_boundary, self.laplacian_idx.ctypes.data_as(C.c_void_p) if as_coded else None, r16,
-                                                0 if as_coded else 1, 0, _lib.ptr(xi[lo:]), m, self.d + 1, _lib.ptr(rows), Mp, s), "gp_cross_rows")
-            _lib.check(lib.scasml_gp_variance(_lib.ptr(L), Mp, _lib.ptr(rows), Mp, m, 1.0, _lib.ptr(var[lo:]), s), "gp_variance")
+            self._solved_rows(L, xi[lo:lo + chunk], r16, rows, var[lo:])
         return var.cpu().numpy() if was_numpy else var
 
     def predict_std(self, x_t_infer):
@@ -582,31 +605,24 @@ class GP(object):
         return np.sqrt(np.maximum(var, 0.0)) if isinstance(var, np.ndarray) else var.clamp_min(0.0).sqrt()
 
     # joint posterior (no counterpart in models/GP.py): covariance between evaluation points and draws from N(mean, cov)
-    def _rows_device(self, x):
-        """(n, d+1) numpy / torch -> (float32 CUDA rows, was_numpy, float16 rows), as predict_variance takes its points."""
-        torch = _lib.require_gpu()
-        was_numpy = not isinstance(x, torch.Tensor)
-        f16_rows = (np.asarray(x).dtype == np.float16) if was_numpy else x.dtype == torch.float16
-        xi = x if not was_numpy else torch.from_numpy(np.ascontiguousarray(np.asarray(x), dtype=np.float32))
-        xi = xi.to(device="cuda", dtype=torch.float32).contiguous()
-        if xi.dim() != 2 or xi.shape[1] != self.d + 1:
-            raise ValueError("points must have shape (n, %d), got %s" % (self.d + 1, tuple(xi.shape)))
-        return xi, was_numpy, bool(f16_rows)
-
-    def _solved_rows(self, L, xi, f16_rows, buf, var):
-        """buf[:len(xi)] <- (L^-1 K(phi, x_i))^T: op-0 feature rows solved in place by scasml_gp_variance (its variances, a by-product, go to var)."""
+    def _cross_rows(self, x_dom, x_bdy, op, xi, out, ld, r16):
+        """out[i] <- the operator-`op` feature row (op = 4: the gradient of the op-0 row) of every float32 device row xi[i] against the collocation
+        sets (x_dom, x_bdy), the fitted ones or a caller's own: the one call of scasml_gp_cross_rows.  x_bdy may be empty; ld: leading dimension of
+        out in doubles; r16: the round16 bits (_gram_bits)."""
         lib = _lib.load()
+        n, nb, step = xi.shape[0], x_bdy.shape[0], int(self.cross_rows_per_call)
+        for lo in range(0, n, step):
+            _lib.check(lib.scasml_gp_cross_rows(self.d, self.a, _lib.ptr(x_dom), x_dom.shape[0], _lib.ptr(x_bdy) if nb else None, nb, self._idx_ptr, r16,
+                                                0 if self.compat == "reference" else 1, op, _lib.ptr(xi[lo:]), min(step, n - lo), self.d + 1,
+                                                _lib.ptr(out[lo:]), ld, _lib.stream_ptr()), "gp_cross_rows")
+
+    def _solved_rows(self, L, xi, r16, buf, var):
+        """buf[:len(xi)] <- (L^-1 K(phi, x_i))^T: op-0 feature rows solved in place by scasml_gp_variance (its variances, a by-product, go to var).
+        buf, (rows x Mp), was ZEROED when it was allocated: the feature rows fill columns 0 .. M, and columns M .. Mp stay zero through every
+        solve, because L is the identity there."""
         n, Mp = xi.shape[0], L.shape[0]
-        as_coded = self.compat == "reference"
-        r16 = self._gram_bits(self._xd, self._xb, f16_rows) if as_coded else 0
-        s = _lib.stream_ptr()
-        buf[:n].zero_()                                                # columns M .. Mp stay zero (L is the identity there)
-        for lo in range(0, n, 65535 * 16):
-            m = min(65535 * 16, n - lo)
-            _lib.check(lib.scasml_gp_cross_rows(self.d, self.a, _lib.ptr(self._xd), self.N_domain, _lib.ptr(self._xb) if self.N_boundary else None,
-                                                self.N_boundary, self.laplacian_idx.ctypes.data_as(C.c_void_p) if as_coded else None, r16,
-                                                0 if as_coded else 1, 0, _lib.ptr(xi[lo:]), m, self.d + 1, _lib.ptr(buf[lo:]), Mp, s), "gp_cross_rows")
-        _lib.check(lib.scasml_gp_variance(_lib.ptr(L), Mp, _lib.ptr(buf), Mp, n, 1.0, _lib.ptr(var), s), "gp_variance")
+        self._cross_rows(self._xd, self._xb, 0, xi, buf, Mp, r16)
+        _lib.check(_lib.load().scasml_gp_variance(_lib.ptr(L), Mp, _lib.ptr(buf), Mp, n, 1.0, _lib.ptr(var), _lib.stream_ptr()), "gp_variance")
         return buf[:n]
 
     def _prior_block(self, xi, yi, f16_ops):
@@ -616,7 +632,6 @@ class GP(object):
         variance_buffer_bytes.  f16_ops (f16_graph, x AND y handed in as float16 arrays) selects the reference's float16 op sequence; it is decided
         by the callers' dtypes, never by the values of a block, so every entry is a function of its own pair, whatever the block."""
         torch = _lib.require_gpu()
-        lib = _lib.load()
         n, m = xi.shape[0], yi.shape[0]
         if self.compat is None:
             x64, y64 = xi.to(torch.float64), yi.to(torch.float64)
@@ -628,14 +643,11 @@ class GP(object):
         out = torch.empty((n, m), dtype=torch.float64, device="cuda")
         r16 = _lib.ROUND16_ENTRIES | (_lib.ROUND16_F16_OPS | self._f16_extra if f16_ops else 0)
         step = int(max(1, min(m, self.variance_buffer_bytes // (32 * n))))
-        rows = torch.empty((min(n, 65535 * 16), 4 * step), dtype=torch.float64, device="cuda")
+        rows = torch.empty((n, 4 * step), dtype=torch.float64, device="cuda")
         for lo in range(0, m, step):
             w = min(step, m - lo)
-            for r0 in range(0, n, rows.shape[0]):
-                h = min(rows.shape[0], n - r0)
-                _lib.check(lib.scasml_gp_cross_rows(self.d, self.a, _lib.ptr(yi[lo:]), w, None, 0, self.laplacian_idx.ctypes.data_as(C.c_void_p), r16, 0, 0,
-                                                    _lib.ptr(xi[r0:]), h, self.d + 1, _lib.ptr(rows), 4 * step, _lib.stream_ptr()), "gp_cross_rows")
-                out[r0:r0 + h, lo:lo + w] = rows[:h, :w]
+            self._cross_rows(yi[lo:lo + w], yi[:0], 0, xi, rows, 4 * step, r16)
+            out[:, lo:lo + w] = rows[:, :w]
         return out
 
     def predict_covariance(self, x_t_infer, y_t_infer=None):
@@ -668,6 +680,8 @@ class GP(object):
         rows_cap = int(max(2, self.variance_buffer_bytes // (8 * Mp)))
         s = _lib.stream_ptr()
         f16_ops = self.f16_graph and f16x and f16y
+        r16x = self._gram_bits(self._xd, self._xb, f16x)
+        r16y = r16x if symmetric else self._gram_bits(self._xd, self._xb, f16y)
 
         def subtract(block, Vx, Vy, lower_only):
             # lower_only (a diagonal block of the symmetric case): the 64 x 64 tiles above the 256-row block diagonal are skipped, then mirrored over
@@ -675,22 +689,22 @@ class GP(object):
                                               0, 1 if lower_only else 0, 0, s), "gemm_nt_sub")
 
         if symmetric and n <= rows_cap:
-            Vx = self._solved_rows(L, xi, f16x, torch.empty((n, Mp), dtype=torch.float64, device="cuda"), torch.empty(n, dtype=torch.float64, device="cuda"))
+            Vx = self._solved_rows(L, xi, r16x, torch.zeros((n, Mp), dtype=torch.float64, device="cuda"), torch.empty(n, dtype=torch.float64, device="cuda"))
             Cm.copy_(self._prior_block(xi, xi, f16_ops))
             subtract(Cm, Vx, Vx, True)
         else:
             cx = int(min(n, rows_cap // 2))
             cy = int(min(m, rows_cap // 2))
-            bx = torch.empty((cx, Mp), dtype=torch.float64, device="cuda")
-            by = torch.empty((cy, Mp), dtype=torch.float64, device="cuda")
+            bx = torch.zeros((cx, Mp), dtype=torch.float64, device="cuda")           # zeroed here, once (_solved_rows)
+            by = torch.zeros((cy, Mp), dtype=torch.float64, device="cuda")
             var = torch.empty(max(cx, cy), dtype=torch.float64, device="cuda")
             for i0 in range(0, n, cx):
-                Vx = self._solved_rows(L, xi[i0:i0 + cx], f16x, bx, var)
+                Vx = self._solved_rows(L, xi[i0:i0 + cx], r16x, bx, var)
                 for j0 in range(0, m, cy):
                     if symmetric and j0 > i0:                          # cx == cy: the blocks above the diagonal are mirrored
                         break
                     diag = symmetric and j0 == i0
-                    Vy = Vx if diag else self._solved_rows(L, yi[j0:j0 + cy], f16y, by, var)
+                    Vy = Vx if diag else self._solved_rows(L, yi[j0:j0 + cy], r16y, by, var)
                     block = Cm[i0:i0 + cx, j0:j0 + cy]
                     block.copy_(self._prior_block(xi[i0:i0 + cx], yi[j0:j0 + cy], f16_ops))
                     subtract(block, Vx, Vy, diag)
@@ -716,8 +730,7 @@ class GP(object):
         was_numpy = not isinstance(x_t_infer, torch.Tensor)
         # the caller's rows in their own dtype, on the device once (float16 rows stay float16 rows for predict and the as-coded entries)
         xdev = torch.from_numpy(np.ascontiguousarray(np.asarray(x_t_infer))).cuda() if was_numpy else x_t_infer
-        if xdev.dim() != 2 or xdev.shape[1] != self.d + 1:
-            raise ValueError("points must have shape (n, %d), got %s" % (self.d + 1, tuple(xdev.shape)))
+        self._check_rows(xdev)
         n = xdev.shape[0]
         npad = _round_up(max(n, 1), 32)
         if 8 * npad * npad > self.variance_buffer_bytes:
@@ -726,14 +739,10 @@ class GP(object):
         if n == 0 or n_samples == 0:
             return np.empty((n_samples, n)) if was_numpy else torch.empty((n_samples, n), dtype=torch.float64, device="cuda")
         mean = self.predict(xdev)[:, 0].to(torch.float64).contiguous()
-        Lc = torch.eye(npad, dtype=torch.float64, device="cuda")
-        Lc[:n, :n] = self.predict_covariance(xdev)
-        info = torch.zeros(1, dtype=torch.int32, device="cuda")
+        Lc, info = self._factor_padded(self.predict_covariance(xdev), jitter, "cholesky(cov)")
+        if info != 0:
+            raise ValueError("cov(x, x) + jitter I is not positive definite at jitter = %g (pivot %d of %d): pass a larger jitter" % (jitter, info, n))
         s = _lib.stream_ptr()
-        _lib.check(lib.scasml_cholesky(_lib.ptr(Lc), npad, jitter, _lib.ptr(info), s), "cholesky(cov)")
-        if int(info.item()) != 0:
-            raise ValueError("cov(x, x) + jitter I is not positive definite at jitter = %g (pivot %d of %d): pass a larger jitter" % (
-                jitter, int(info.item()), n))
         seed = int(seed) & 0xFFFFFFFFFFFFFFFF
         if not was_numpy:                                              # the caller's tensor is the whole output anyway: one launch
             out = torch.empty((n_samples, n), dtype=torch.float64, device="cuda")
@@ -774,32 +783,15 @@ class GP(object):
     def _cross(self, op, x_t_infer, x_t_domain, x_t_boundary):
         """(N_inf, M) rows of operator `op` (or, op = 4, the (N_inf, M, d+1) gradient of the op-0 rows) against the given collocation sets."""
         torch = _lib.require_gpu()
-        lib = _lib.load()
-        was_numpy = not isinstance(x_t_infer, torch.Tensor)
-        f16_rows = (np.asarray(x_t_infer).dtype == np.float16) if was_numpy else x_t_infer.dtype == torch.float16
-
-        def dev(x):
-            t = x if isinstance(x, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(np.asarray(x), dtype=np.float32))
-            t = t.to(device="cuda", dtype=torch.float32).contiguous().reshape(-1, self.d + 1)
-            return t
-        xi, xd = dev(x_t_infer), dev(x_t_domain)
-        xb = dev(x_t_boundary) if x_t_boundary is not None and len(x_t_boundary) else torch.zeros((0, self.d + 1), dtype=torch.float32, device="cuda")
-        nd, nb, ni = xd.shape[0], xb.shape[0], xi.shape[0]
-        if nd < 1:
+        xi, was_numpy, f16_rows = self._rows_device(x_t_infer, flat=True)
+        xd = self._rows_device(x_t_domain, flat=True)[0]
+        xb = self._rows_device(x_t_boundary, flat=True)[0] if x_t_boundary is not None and len(x_t_boundary) else xd[:0]
+        if xd.shape[0] < 1:
             raise ValueError("the cross-kernel builders need at least one domain point")
-        M = 4 * nd + nb
-        as_coded = self.compat == "reference"
-        r16 = self._gram_bits(xd, xb, f16_rows) if as_coded else 0
-        shape = (ni, M, self.d + 1) if op == 4 else (ni, M)
-        out = torch.empty(shape, dtype=torch.float64, device="cuda")
-        if ni:
-            rows_per_call = 65535 * 16
-            for lo in range(0, ni, rows_per_call):
-                n = min(rows_per_call, ni - lo)
-                _lib.check(lib.scasml_gp_cross_rows(self.d, self.a, _lib.ptr(xd), nd, _lib.ptr(xb) if nb else None, nb,
-                                                    self.laplacian_idx.ctypes.data_as(C.c_void_p) if as_coded else None, r16, 0 if as_coded else 1, op,
-                                                    _lib.ptr(xi[lo:]), n, self.d + 1, _lib.ptr(out[lo:]), M, _lib.stream_ptr()), "gp_cross_rows")
-        if as_coded:
+        ni, M = xi.shape[0], 4 * xd.shape[0] + xb.shape[0]
+        out = torch.empty((ni, M, self.d + 1) if op == 4 else (ni, M), dtype=torch.float64, device="cuda")
+        self._cross_rows(xd, xb, op, xi, out, M, self._gram_bits(xd, xb, f16_rows))
+        if self.compat == "reference":
             out = out.to(torch.float16)                               # exact: the entries are float16 values
         return out.cpu().numpy() if was_numpy else out
 
@@ -839,7 +831,7 @@ class GP(object):
         if opx == "grad":
             g = self._cross(4, x, y, None)[0, 0]
             return g
-        return self._cross(self._OPS[opx], x, y, None)[0, {"I": 0, "lap": 1, "dt": 2, "div": 3}[opy]]
+        return self._cross(self._OPS[opx], x, y, None)[0, self._OPS[opy]]
 
     def kappa(self, x_t, y_t):
         '''K(x_t, y_t) for single vectors (models/GP.py:41-43).'''
