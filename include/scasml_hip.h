@@ -158,6 +158,31 @@ int scasml_picard_tree(const scasml_problem *prob_h, const scasml_plan *plan_h, 
                        float *out_uz, float *out_uhat, void *stream);
 
 /*
+ * scasml_picard_tree plus the Monte-Carlo standard error of every root's u (the same routines of the reference as above: solvers/MLP.py:141-274,
+ * solvers/ScaSML.py:149-284, solvers/MLP_full_history.py:64-180, solvers/ScaSML_full_history.py:75-199; the reference has no counterpart
+ * for the error itself).  (u, z) and u_hat are bit for bit those of scasml_picard_tree with the same arguments.
+ *   mode   : SCASML_MODE_MLP or SCASML_MODE_ACCUMULATE.  GENERATE has no estimate (run scasml_picard_tree): SCASML_ERR_ARG.
+ *   out_se : B floats, required.
+ * Definition.  The root call at level n computes u = T_g + sum_{l<n} T_l.
+ *   T_g = sum_{m<mg} Y_{g,m}: Y_{g,m} = g(X_T^m) / mg [MLP], (g - u_hat)(X_T^m) / mg [ACCUMULATE]; N_g = mg = plan.mg[n].
+ *   T_l = sum_{m<mc} Y_{l,m}: Y_{l,m} is everything sample path m of term plan.term[n][l] adds to u -- over its q nodes the "+" addend,
+ *         the "-" addend (l > 0) and, in ACCUMULATE at l = 0, the surrogate's residual addend, each with its factor 1 / mc; N_l = mc.
+ *   Every summand owns its RNG sites: the summands of a term are i.i.d. given the root, and the terms independent of each other (inner
+ *   calls are clipped inside a summand, which does not disturb this).
+ *   Var(u) ~= sum_j N_j / (N_j - 1) sum_i (Y_{j,i} - mean_j)^2, accumulated per term on the deviations from its first summand (exactly 0
+ *   where the samples coincide, as at t = T);  out_se = sqrt(max(Var, 0)) in float32.
+ *   It is the Monte-Carlo error of the UNCLIPPED root sum: the clip of the returned u is not modelled, the Picard truncation bias is not
+ *   included and, in ACCUMULATE, neither is the surrogate's own error (u_hat is deterministic given the fit: se(u_hat + u) = se(u)).
+ * SCASML_ERR_UNSUPPORTED (scasml_last_error names the cause): rng.world != 1 (sample-sharded units split a path's addends across ranks:
+ * sums of squares do not add); rng.flags != 0 (COMPAT_CRN shares draws between summands, JAX_STREAM and COMPAT_F16 are parity modes);
+ * plan.mg[n] < 2 or any plan.term[n][l].mc < 2 (one sample has no estimable variance: quadrature rho <= 2, full history M = 1) -- such
+ * plans are refused, never answered with a partial number.  plan.n == 0: out_uz and out_se are zeros.  B == 0 does nothing.
+ */
+int scasml_picard_tree_stderr(const scasml_problem *prob_h, const scasml_plan *plan_h, int mode, const float *x_t, int64_t B,
+                              int64_t site_stride, scasml_rng rng, float *points, const float *gp_vals,
+                              float *out_uz, float *out_uhat, float *out_se, void *stream);
+
+/*
  * Staged Picard tree, for equations whose f and g are not in the registry (the driver evaluates them as batched torch
  * functions between launches; solvers/_picard.py).  A level-n solve runs SCASML_MODE_GENERATE of scasml_picard_tree once
  * (its points do not depend on the equation), then stages S = 1 .. n, each computing the (u, z) of every level-S subtree

@@ -79,13 +79,8 @@ __global__ void debug_jax_normals_kernel(uint32_t k0, uint32_t k1, uint64_t inde
     if (i < count) out[i] = jax_normal_f16(k0, k1, index0 + (uint64_t)i);
 }
 
-}  // namespace scasml
-
-using namespace scasml;
-
-extern "C" int scasml_picard_tree(const scasml_problem *prob, const scasml_plan *plan, int mode, const float *x_t,
-                                  int64_t B, int64_t site_stride, scasml_rng rng, float *points, const float *gp_vals, float *out_uz,
-                                  float *out_uhat, void *stream) {
+int picard_tree_run(const scasml_problem *prob, const scasml_plan *plan, int mode, const float *x_t, int64_t B, int64_t site_stride, scasml_rng rng,
+                    float *points, const float *gp_vals, float *out_uz, float *out_uhat, float *out_se, bool want_se, void *stream) {
     if (!prob || !plan) return fail(SCASML_ERR_ARG, "picard_tree: null argument");
     if (B < 0) return fail(SCASML_ERR_ARG, "picard_tree: negative batch");
     if (site_stride != 0 && site_stride < B) return fail(SCASML_ERR_ARG, "picard_tree: site_stride %lld is smaller than the batch %lld", (long long)site_stride, (long long)B);
@@ -109,12 +104,28 @@ extern "C" int scasml_picard_tree(const scasml_problem *prob, const scasml_plan 
             const scasml_term &t = plan->term[np][l];
             if (t.q < 1 || t.q > SCASML_MAX_Q || t.mc < 1) return fail(SCASML_ERR_ARG, "picard_tree: bad term [%d][%d]", np, l);
         }
+    if (want_se) {   // scasml_picard_tree_stderr: what has no estimate is refused, never answered with a partial number
+        if (mode != SCASML_MODE_MLP && mode != SCASML_MODE_ACCUMULATE)
+            return fail(SCASML_ERR_ARG, "picard_tree_stderr: mode %d has no estimate (SCASML_MODE_MLP or SCASML_MODE_ACCUMULATE)", mode);
+        if (!out_se) return fail(SCASML_ERR_ARG, "picard_tree_stderr: out_se is null");
+        if (rng.world != 1)
+            return fail(SCASML_ERR_UNSUPPORTED, "picard_tree_stderr: world = %d: sample-sharded units split a path's addends across ranks, whose sums of squares do not add", rng.world);
+        if (rng.flags != 0)
+            return fail(SCASML_ERR_UNSUPPORTED, "picard_tree_stderr: rng.flags = %u: SCASML_RNG_COMPAT_CRN shares draws between summands, SCASML_RNG_JAX_STREAM and "
+                        "SCASML_RNG_COMPAT_F16 are parity modes; the estimate needs flags = 0", rng.flags);
+        if (plan->n > 0 && plan->mg[plan->n] < 2)
+            return fail(SCASML_ERR_UNSUPPORTED, "picard_tree_stderr: the terminal term of level %d has %d sample: no estimable variance", plan->n, plan->mg[plan->n]);
+        for (int l = 0; l < plan->n; ++l)
+            if (plan->term[plan->n][l].mc < 2)
+                return fail(SCASML_ERR_UNSUPPORTED, "picard_tree_stderr: term [%d][%d] has %d sample path: no estimable variance", plan->n, l, plan->term[plan->n][l].mc);
+    }
     hipStream_t s = (hipStream_t)stream;
     if (plan->n == 0) {  // MLP.py:205-207: zeros (ScaSML: u_hat still requested by the caller through gp_eval)
         if (mode != SCASML_MODE_GENERATE) {
             if (hipMemsetAsync(out_uz, 0, sizeof(float) * B * (prob->d + 1), s) != hipSuccess)
                 return fail(SCASML_ERR_HIP, "picard_tree: memset failed");
         }
+        if (want_se && hipMemsetAsync(out_se, 0, sizeof(float) * B, s) != hipSuccess) return fail(SCASML_ERR_HIP, "picard_tree_stderr: memset failed");
         return 0;
     }
     TreeArgs a;
@@ -124,6 +135,7 @@ extern "C" int scasml_picard_tree(const scasml_problem *prob, const scasml_plan 
     a.gpv = reinterpret_cast<const float4 *>(gp_vals);
     a.out_uz = out_uz;
     a.out_uhat = out_uhat;
+    a.out_se = want_se ? out_se : nullptr;
     a.B = B;
     a.Bs = site_stride ? site_stride : B;
     a.ppr = (int64_t)plan->sites[plan->n] + 1;
@@ -152,6 +164,10 @@ extern "C" int scasml_picard_tree(const scasml_problem *prob, const scasml_plan 
     const int64_t blocks = (waves + 3) / 4;
     if (blocks > 0x7FFFFFFF) return fail(SCASML_ERR_UNSUPPORTED, "picard_tree: batch too large");
     const dim3 grid((unsigned)blocks);
+    if (want_se) {   // instantiated in translation units of their own (picard_tree.hpp)
+        if (plan->n > 3) return launch_tree_stderr_deep(a, plan->variant, mode, prob->eq_id, plan->n, grid, s);
+        return launch_tree_stderr(a, plan->variant, mode, prob->eq_id, plan->n, grid, s);
+    }
     if (eq_mlp_only(prob->eq_id)) {
         constexpr int EQ2 = SCASML_EQ_QUADRATIC_GRADIENT_REACTION_DIFFUSION;
         return plan->variant == 0 ? launch_level<0, SCASML_MODE_MLP, EQ2>(a, plan->n, grid, s) : launch_level<1, SCASML_MODE_MLP, EQ2>(a, plan->n, grid, s);
@@ -159,6 +175,16 @@ extern "C" int scasml_picard_tree(const scasml_problem *prob, const scasml_plan 
     int rc = SCASML_ERR_UNSUPPORTED;
     SCASML_EQ_SWITCH(prob->eq_id, rc = (plan->variant == 0 ? launch_mode<0, EQ>(a, mode, plan->n, grid, s) : launch_mode<1, EQ>(a, mode, plan->n, grid, s)));
     return rc;
+}
+
+}  // namespace scasml
+
+using namespace scasml;
+
+extern "C" int scasml_picard_tree(const scasml_problem *prob, const scasml_plan *plan, int mode, const float *x_t,
+                                  int64_t B, int64_t site_stride, scasml_rng rng, float *points, const float *gp_vals, float *out_uz,
+                                  float *out_uhat, void *stream) {
+    return picard_tree_run(prob, plan, mode, x_t, B, site_stride, rng, points, gp_vals, out_uz, out_uhat, nullptr, false, stream);
 }
 
 extern "C" int scasml_debug_jax_normals(uint32_t key0, uint32_t key1, uint64_t index0, int64_t count, float *out, void *stream) {

@@ -1,5 +1,6 @@
 // Picard-tree walker and kernel template, shared by the translation units that instantiate it (picard_tree.hip: the Philox stream,
-// picard_tree_jax.hip / picard_tree_jax_deep.hip: the reference's own stream, SCASML_RNG_JAX_STREAM) -- split so that the build compiles
+// picard_tree_jax.hip / picard_tree_jax_deep.hip: the reference's own stream, SCASML_RNG_JAX_STREAM; picard_tree_stderr.hip /
+// picard_tree_stderr_deep.hip: the kernels that also estimate the standard error of u) -- split so that the build compiles
 // the instantiations in parallel (the JAX-stream kernels inline one Threefry + erf_inv per normal at every site of the unrolled tree).
 #pragma once
 #include <string.h>
@@ -27,6 +28,7 @@ struct TreeArgs {
     const uint32_t *jk;   // SCASML_RNG_JAX_STREAM: key words [terminal k0 k1 | path sub-key 0 k0 k1 | sub-key 1 ...] (scasml_rng.jax_keys)
     int32_t d, G, logG, kp;
     float T, mu, sigma, clip;
+    float *out_se;   // picard_tree_kernel<..., SE = true> only: B standard errors of the root call's u (scasml_picard_tree_stderr)
 };
 
 __device__ __forceinline__ float4 f4(float v) { return make_float4(v, v, v, v); }
@@ -146,9 +148,43 @@ struct PrefetchQueue {
 template <>
 struct PrefetchQueue<false> {};
 
-template <int VAR, int MODE, int EQ, bool JAX = false>
+// Monte-Carlo variance of the ROOT call's u (scasml_picard_tree_stderr, DESIGN.md "Standard errors"): the root sum is a sum of independent
+// terms -- the terminal samples, then one term per level l < n -- and every term a sum of N i.i.d. summands Y_0 .. Y_{N-1} that the walk
+// visits one after another.  A term accumulates the deviations from its FIRST summand, D_i = Y_i - Y_0 (S1 = sum D_i, S2 = sum D_i^2), and
+// closes with N / (N - 1) (S2 - S1^2 / N): near t = T, where every sample of g coincides, a float32 sum of Y^2 would cancel to noise and
+// this form gives exactly 0.  Every lane of a root's group holds the same Y (dim_sum is group-uniform): no shuffles.
+template <bool ON>
+struct SeTerm {
+    float y0, s1, s2;
+    __device__ __forceinline__ void begin() { y0 = s1 = s2 = 0.0f; }
+    __device__ __forceinline__ void add(float y, bool first) {
+        if (first) {
+            y0 = y;
+        } else {
+            const float dv = y - y0;
+            s1 += dv;
+            s2 = fmaf(dv, dv, s2);
+        }
+    }
+    // N >= 2 (the entry point refuses a term of one sample)
+    __device__ __forceinline__ float close(int N) const {
+        const float fn = (float)N;
+        return (fn / (fn - 1.0f)) * fmaf(-s1 / fn, s1, s2);
+    }
+};
+template <>
+struct SeTerm<false> {};
+template <bool ON>
+struct SeState {
+    float var;
+};
+template <>
+struct SeState<false> {};
+
+template <int VAR, int MODE, int EQ, bool JAX = false, bool SE = false>
 struct Walker {
     const TreeArgs &a;
+    SeState<SE> se;    // SE: the variance estimate of the root call's u, summed over its terms (TOP frames only)
     float4 mask;       // 1 on this lane's live spatial dims, 0 on padding
     float4 tmask;      // 1 on the component that holds t in a stored row (column d)
     uint32_t row_off4; // (local * kp + 4 * gl) / 4: this lane's float4 inside a site's block of B rows
@@ -258,8 +294,11 @@ struct Walker {
         const int q = tm.q, mc = tm.mc;
         const uint32_t s_l = (uint32_t)tm.sites_l, s_lm = (uint32_t)tm.sites_lm1;
         const float inv_mc = rcp_fast((float)mc);
+        SeTerm<SE && TOP> st;
+        if constexpr (SE && TOP) st.begin();
         for (int m = 0; m < mc; ++m) {
             float4 X = x, W = f4(0.0f);
+            float ym = 0.0f;                                     // SE: what sample path m adds to u (unused otherwise)
             // compat_crn: the children of every node k draw their terminal normals where the k = 0 children do
             // (MLP.py:167-168,178: one fixed key per uz_solve call, so calls of equal shape share their draws)
             const uint32_t c_plus = cbase + o + 1u, c_minus = c_plus + s_l;
@@ -365,6 +404,7 @@ struct Walker {
                     if constexpr (MODE != SCASML_MODE_GENERATE) {
                         const float y = f_eval(uc, zc, gp) * (wk * inv_mc);
                         u += y;                                  // MLP.py:248
+                        if constexpr (SE && TOP) ym += y;
                         z = fma4(y * dplus, wvec, z);            // MLP.py:249
                     }
                 }
@@ -375,6 +415,7 @@ struct Walker {
                         if constexpr (MODE != SCASML_MODE_GENERATE) {
                             const float y = f_eval(uc, zc, gp) * (wk * inv_mc);
                             u -= y;                              // MLP.py:269
+                            if constexpr (SE && TOP) ym -= y;
                             z = fma4(-y * dminus, wvec, z);      // MLP.py:271
                         }
                     }
@@ -382,10 +423,13 @@ struct Walker {
                 } else if constexpr (MODE == SCASML_MODE_ACCUMULATE) {
                     const float e = gp.z * (wk * inv_mc);        // ScaSML.py:274-280 (l = 0: one addend, mine)
                     u += e;
+                    if constexpr (SE && TOP) ym += e;
                     z = fma4(e * dminus, wvec, z);
                 }
             }
+            if constexpr (SE && TOP) st.add(ym, m == 0);
         }
+        if constexpr (SE && TOP) se.var += st.close(mc);
         if constexpr (L + 1 < N) level<N, L + 1, TOP>(x, t, tau, base, cbase, o, u, z, jrow, jfirst + (uint32_t)q * (1u + nsplits<L>() + nsplits<L - 1>()));
     }
 
@@ -421,6 +465,8 @@ struct Walker {
                     }
                 }
             }
+            SeTerm<SE && TOP> st;
+            if constexpr (SE && TOP) st.begin();
             for (int m = 0; m < mg; ++m) {                       // MLP.py:175-202
                 const uint32_t site = base + (uint32_t)m;
                 float4 nrm, XT, gpv = f4(0.0f);
@@ -464,10 +510,12 @@ struct Walker {
                 } else {
                     const float g = g_terminal(XT, gpv.x);
                     su += g;
+                    if constexpr (SE && TOP) st.add(g, m == 0);
                     sz = fma4(g, nrm, sz);
                 }
             }
             const float inv_mg = rcp_fast((float)mg);
+            if constexpr (SE && TOP) se.var += st.close(mg) * (inv_mg * inv_mg);   // the summands are g / mg
             float u = su * inv_mg;
             const float zs = inv_mg * rcp_fast(VAR == 0 ? tau + 1e-6f : tau);   // MLP.py:201 / MLP_full_history.py:122
             // padding dims carry sz = 0: at T - t = 0 the full-history scale is 1/0 (MLP_full_history.py:122 has no epsilon) and
@@ -493,8 +541,9 @@ struct Walker {
 
 // (An occupancy hint for ACCUMULATE was measured, profiles/r02_accumulate_prefetch.txt: 5 waves/SIMD 1.22 ms against 1.26, but the
 // deeper levels then spill inside their loops; 6 and 8 are slower.  No hint.)
-template <int VAR, int MODE, int N, int EQ, bool JAX = false>
+template <int VAR, int MODE, int N, int EQ, bool JAX = false, bool SE = false>
 __global__ __launch_bounds__(256) void picard_tree_kernel(const TreeArgs a) {
+    static_assert(!SE || (!JAX && MODE != SCASML_MODE_GENERATE), "standard errors: MLP and ACCUMULATE on the Philox stream");
     if constexpr (JAX) jax_table_to_lds();   // every thread, before any return below: the reference's stream needs its own 4 KB table only
     else normal_table_to_lds();
     const int lane = threadIdx.x & 63;
@@ -517,7 +566,8 @@ __global__ __launch_bounds__(256) void picard_tree_kernel(const TreeArgs a) {
     const bool valid = local < a.B;
     if (!valid) local = a.B - 1;  // idle lanes shadow the last root; their stores are masked
 
-    Walker<VAR, MODE, EQ, JAX> w{a};
+    Walker<VAR, MODE, EQ, JAX, SE> w{a};
+    if constexpr (SE) w.se.var = 0.0f;
     w.gl = gl;
     w.root = a.root0 + (uint32_t)local;
     w.local = local;
@@ -552,6 +602,7 @@ __global__ __launch_bounds__(256) void picard_tree_kernel(const TreeArgs a) {
                 if constexpr (MODE == SCASML_MODE_ACCUMULATE) {
                     if (a.out_uhat) a.out_uhat[local] = w.gp_at((uint32_t)(a.ppr - 1)).x;
                 }
+                if constexpr (SE) a.out_se[local] = sqrtf(fmaxf(w.se.var, 0.0f));
             }
             if (dim0 + 0 < a.d) out[1 + dim0 + 0] = z.x;
             if (dim0 + 1 < a.d) out[1 + dim0 + 1] = z.y;
@@ -564,5 +615,11 @@ __global__ __launch_bounds__(256) void picard_tree_kernel(const TreeArgs a) {
 // the reference's own random stream (compat_rng = "jax"): instantiated in picard_tree_jax.hip (n <= 3) and picard_tree_jax_deep.hip (n = 4, 5)
 int launch_tree_jax(const TreeArgs &a, int variant, int mode, int eq_id, int n, dim3 grid, hipStream_t s);
 int launch_tree_jax_deep(const TreeArgs &a, int variant, int mode, int eq_id, int n, dim3 grid, hipStream_t s);
+// the kernels that also estimate the standard error of u (SE = true): picard_tree_stderr.hip (n <= 3) and picard_tree_stderr_deep.hip (n = 4, 5)
+int launch_tree_stderr(const TreeArgs &a, int variant, int mode, int eq_id, int n, dim3 grid, hipStream_t s);
+int launch_tree_stderr_deep(const TreeArgs &a, int variant, int mode, int eq_id, int n, dim3 grid, hipStream_t s);
+// scasml_picard_tree and scasml_picard_tree_stderr (out_se non-null selects the latter's kernels): one validation, one launch geometry
+int picard_tree_run(const scasml_problem *prob, const scasml_plan *plan, int mode, const float *x_t, int64_t B, int64_t site_stride, scasml_rng rng,
+                    float *points, const float *gp_vals, float *out_uz, float *out_uhat, float *out_se, bool want_se, void *stream);
 
 }  // namespace scasml

@@ -40,12 +40,17 @@ class MLP:
     def approx_parameters(self, rhomax):
         return tables.approx_parameters(int(rhomax), float(self.T))   # :111-139 (cached)
 
-    def uz_solve(self, n, rho, x_t):
-        '''(batch, 1 + d): u and z of solvers/MLP.py:141-274.'''
+    def uz_solve(self, n, rho, x_t, return_stderr=False):
+        '''(batch, 1 + d): u and z of solvers/MLP.py:141-274.  return_stderr=True: (uz, se), se the (batch, 1) float32 Monte-Carlo standard
+        error of u (of the unclipped root sum; the Picard truncation bias is not in it): scasml_picard_tree_stderr in include/scasml_hip.h.
+        ValueError where a term of the root call has one sample (rho <= 2).'''
         self.Mf, self.Mg, self.Q, self.c, self.w = self.approx_parameters(rho)
-        uz, _, was_numpy = self._engine.solve(int(n), int(rho), x_t)
+        uz, _, was_numpy, *se = self._engine.solve(int(n), int(rho), x_t, stderr=bool(return_stderr))
         self.evaluation_counter += self._engine.evaluation_increment(int(n), int(rho))
-        return deliver(uz, was_numpy)
+        return (deliver(uz, was_numpy), deliver(se[0][:, None], was_numpy)) if return_stderr else deliver(uz, was_numpy)
 
-    def u_solve(self, n, rho, x_t):
+    def u_solve(self, n, rho, x_t, return_stderr=False):
+        if return_stderr:
+            uz, se = self.uz_solve(n, rho, x_t, return_stderr=True)
+            return uz[:, 0:1], se
         return self.uz_solve(n, rho, x_t)[:, 0:1]                 # :276-288

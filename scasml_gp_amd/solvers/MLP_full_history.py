@@ -27,11 +27,16 @@ class MLP_full_history:
     def g(self, x_t):
         return self.equation.g(x_t)[:, 0]
 
-    def uz_solve(self, n, rho, x_t, M):
-        '''solvers/MLP_full_history.py:64-180 (rho is ignored there as well).'''
-        uz, _, was_numpy = self._engine.solve(int(n), int(M), x_t)
+    def uz_solve(self, n, rho, x_t, M, return_stderr=False):
+        '''solvers/MLP_full_history.py:64-180 (rho is ignored there as well).  return_stderr=True: (uz, se), se the (batch, 1) float32
+        Monte-Carlo standard error of u (of the unclipped root sum; the Picard truncation bias is not in it): scasml_picard_tree_stderr in
+        include/scasml_hip.h.  ValueError for M = 1 (one sample per term).'''
+        uz, _, was_numpy, *se = self._engine.solve(int(n), int(M), x_t, stderr=bool(return_stderr))
         self.evaluation_counter += self._engine.evaluation_increment(int(n), int(M))
-        return deliver(uz, was_numpy)
+        return (deliver(uz, was_numpy), deliver(se[0][:, None], was_numpy)) if return_stderr else deliver(uz, was_numpy)
 
-    def u_solve(self, n, rho, x_t, M=3):
+    def u_solve(self, n, rho, x_t, M=3, return_stderr=False):
+        if return_stderr:
+            uz, se = self.uz_solve(n, rho, x_t, M, return_stderr=True)
+            return uz[:, 0:1], se
         return self.uz_solve(n, rho, x_t, M)[:, 0:1]              # :182-196

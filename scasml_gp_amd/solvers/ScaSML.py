@@ -50,22 +50,28 @@ class ScaSML:
     def approx_parameters(self, rhomax):
         return tables.approx_parameters(int(rhomax), float(self.T))
 
-    def _solve(self, n, par, x_t):
-        uz, uhat, was_numpy = self._engine.solve(int(n), int(par), x_t)
+    def _solve(self, n, par, x_t, stderr=False):
+        """-> (uz, u_hat, was_numpy, se): se the (batch, 1) standard error of u_breve, or None."""
+        uz, uhat, was_numpy, *se = self._engine.solve(int(n), int(par), x_t, stderr=bool(stderr))
         self.evaluation_counter += self._engine.evaluation_increment(int(n), int(par))
-        return uz, uhat, was_numpy
+        return uz, uhat, was_numpy, (se[0][:, None] if stderr else None)
 
-    def uz_solve(self, n, rho, x_t):
-        '''solvers/ScaSML.py:149-284.'''
+    def uz_solve(self, n, rho, x_t, return_stderr=False):
+        '''solvers/ScaSML.py:149-284.  return_stderr=True: (uz, se), se the (batch, 1) float32 Monte-Carlo standard error of u_breve
+        (scasml_picard_tree_stderr in include/scasml_hip.h); ValueError where a term of the root call has one sample (rho <= 2).'''
         self.Mf, self.Mg, self.Q, self.c, self.w = self.approx_parameters(rho)       # :161
-        uz, _, was_numpy = self._solve(n, rho, x_t)
-        return deliver(uz, was_numpy)
+        uz, _, was_numpy, se = self._solve(n, rho, x_t, return_stderr)
+        return (deliver(uz, was_numpy), deliver(se, was_numpy)) if return_stderr else deliver(uz, was_numpy)
 
-    def u_solve(self, n, rho, x_t):
-        '''u_hat + u_breve, solvers/ScaSML.py:286-304.'''
+    def u_solve(self, n, rho, x_t, return_stderr=False):
+        '''u_hat + u_breve, solvers/ScaSML.py:286-304.  return_stderr=True: (u, se) with se the (batch, 1) float32 standard error of the
+        CORRECTION u_breve: u_hat is deterministic given the fit, so se(u_hat + u_breve) = se(u_breve).  It is the Monte-Carlo error of the
+        unclipped Picard sum on the defect and nothing else: the surrogate's own error (GP.predict_variance) and the Picard truncation
+        bias are not in it, and the clip of u_breve is not modelled.'''
         self.Mf, self.Mg, self.Q, self.c, self.w = self.approx_parameters(rho)
-        uz, uhat, was_numpy = self._solve(n, rho, x_t)
-        return deliver(self._sum16(uz[:, 0:1] + uhat[:, None]), was_numpy)
+        uz, uhat, was_numpy, se = self._solve(n, rho, x_t, return_stderr)
+        u = deliver(self._sum16(uz[:, 0:1] + uhat[:, None]), was_numpy)
+        return (u, deliver(se, was_numpy)) if return_stderr else u
 
     def _sum16(self, total):
         """compat_f16: u_breve + u_hat is a float16 sum in the reference (:300-304: u_breve float16 by :284 -- in the full-history solver by

@@ -170,8 +170,22 @@ class PicardEngine:
         p.clip = float(eq.uncertainty if self.gp is not None else eq.norm_estimation)
         return p
 
-    def solve(self, n, par, x_t, root0=0, rank=0, world=1, stream_id=None):
-        """-> (uz (B, 1+d), u_hat (B,) or None) as torch CUDA tensors, plus was_numpy."""
+    def stderr_supported(self, n, par):
+        """(ok, reason): can ``solve(n, par, ..., stderr=True)`` estimate the standard error of u?  Host only, from the plan: a term of the
+        root call with ONE sample has no estimable variance (quadrature rho <= 2, full history M = 1) and such a plan is refused, never
+        answered with a partial number."""
+        plan = self.plan(n, par)
+        if n > 0 and int(plan.mg[n]) < 2:
+            return False, "the terminal term of level %d has %d sample: no estimable variance" % (n, int(plan.mg[n]))
+        for l in range(n):
+            if int(plan.term[n][l].mc) < 2:
+                return False, "term [%d][%d] has %d sample path: no estimable variance" % (n, l, int(plan.term[n][l].mc))
+        return True, ""
+
+    def solve(self, n, par, x_t, root0=0, rank=0, world=1, stream_id=None, stderr=False):
+        """-> (uz (B, 1+d), u_hat (B,) or None) as torch CUDA tensors, plus was_numpy; with ``stderr`` also, last, the (B,) float32 Monte-Carlo
+        standard error of u (scasml_picard_tree_stderr in include/scasml_hip.h: the definition, what it covers and what it leaves out).
+        The call counter moves as in a plain solve, so calls with and without error bars can be mixed without moving any call's stream."""
         torch = _lib.require_gpu()
         lib = _lib.load()
         x, was_numpy, x_max = _as_device(x_t, torch)
@@ -181,6 +195,16 @@ class PicardEngine:
         B = x.shape[0]
         if self.callbacks and world > 1:
             raise NotImplementedError("equation %s has torch callbacks: a staged solve is not sample-sharded" % type(self.equation).__name__)
+        if stderr:
+            if self.callbacks:
+                raise NotImplementedError("equation %s has torch callbacks: the staged tree has no standard-error estimate" % type(self.equation).__name__)
+            ok, why = self.stderr_supported(n, par)
+            if not ok:
+                raise ValueError("no standard error for n = %d, %s = %d: %s" % (n, "rho" if self.variant == "quad" else "M", par, why))
+            if world != 1 or self.compat_crn or self.compat_f16 or self.compat_rng is not None:
+                raise _lib.ScasmlError("picard_tree_stderr: the estimate needs an unsharded solve (world = 1) on the Philox stream without compat_crn, "
+                                       "compat_f16 or compat_rng: sharded units split a path's addends across ranks, compat_crn shares draws between "
+                                       "summands, the others are parity modes")
         plan, prob = self.plan(n, par), self.problem()
         if self.gp is not None and float(getattr(self.gp, "T", self.equation.T)) != float(self.equation.T):
             # the GP folds its terminal time into packed row constants (site kind 3); the tree emits terminal points at the equation's T
@@ -201,11 +225,17 @@ class PicardEngine:
         if stream_id is None:
             self.calls += 1
         out = torch.empty((B, d + 1), dtype=torch.float32, device="cuda")
+        se = torch.empty((B,), dtype=torch.float32, device="cuda") if stderr else None
         s = _lib.stream_ptr()
         if self.callbacks:
             self._solve_staged(n, par, plan, prob, x, out, rng, s)
             return out, None, was_numpy
         if self.gp is None:
+            if stderr:
+                _lib.check(self._timed("picard_mlp_stderr", lambda: lib.scasml_picard_tree_stderr(
+                    C.byref(prob), C.byref(plan), _lib.MODE_MLP, _lib.ptr(x), B, 0, rng, None, None, _lib.ptr(out), None, _lib.ptr(se), s)),
+                    "picard_tree_stderr")
+                return out, None, was_numpy, se
             _lib.check(self._timed("picard_mlp", lambda: lib.scasml_picard_tree(
                 C.byref(prob), C.byref(plan), _lib.MODE_MLP, _lib.ptr(x), B, 0, rng, None, None, _lib.ptr(out), None, s)), "picard_tree")
             self._jax_commit(jax_next, stream_id)
@@ -234,14 +264,22 @@ class PicardEngine:
                     C.byref(prob), C.byref(plan), _lib.MODE_GENERATE, _lib.ptr(xc), nb, stride, rng_c,
                     _lib.ptr(pts), None, None, None, s)), "picard_tree(generate)")
                 self._timed("gp_eval", lambda: self.gp._eval_rows(pts, stride * ppr, stride, kinds, vals, x_bound=x_bound, order=order))
-                _lib.check(self._timed("picard_accumulate", lambda: lib.scasml_picard_tree(
-                    C.byref(prob), C.byref(plan), _lib.MODE_ACCUMULATE, _lib.ptr(xc), nb, stride, rng_c,
-                    _lib.ptr(pts), _lib.ptr(vals), _lib.ptr(ob), _lib.ptr(ub), s)), "picard_tree(accumulate)")
+                if stderr:
+                    sb = se[b0:b0 + nb]
+                    _lib.check(self._timed("picard_accumulate_stderr", lambda: lib.scasml_picard_tree_stderr(
+                        C.byref(prob), C.byref(plan), _lib.MODE_ACCUMULATE, _lib.ptr(xc), nb, stride, rng_c,
+                        _lib.ptr(pts), _lib.ptr(vals), _lib.ptr(ob), _lib.ptr(ub), _lib.ptr(sb), s)), "picard_tree_stderr(accumulate)")
+                else:
+                    _lib.check(self._timed("picard_accumulate", lambda: lib.scasml_picard_tree(
+                        C.byref(prob), C.byref(plan), _lib.MODE_ACCUMULATE, _lib.ptr(xc), nb, stride, rng_c,
+                        _lib.ptr(pts), _lib.ptr(vals), _lib.ptr(ob), _lib.ptr(ub), s)), "picard_tree(accumulate)")
             else:                          # n == 0: zeros (ScaSML.py:217-219); u_hat still needed by u_solve
                 out[b0:b0 + nb].zero_()
                 uhat[b0:b0 + nb] = self.gp._predict_device(xc)[:, 0]
+                if stderr:
+                    se[b0:b0 + nb].zero_()
         self._jax_commit(jax_next, stream_id)
-        return out, uhat, was_numpy
+        return (out, uhat, was_numpy, se) if stderr else (out, uhat, was_numpy)
 
     def stage_lists(self, n, par):
         """Device lists of a staged solve (scasml_plan_stage_list), uploaded once per plan: int32 (base, origin) pairs per stage 1..n for
