@@ -171,6 +171,8 @@ int scasml_picard_tree(const scasml_problem *prob_h, const scasml_plan *plan_h, 
  *   calls are clipped inside a summand, which does not disturb this).
  *   Var(u) ~= sum_j N_j / (N_j - 1) sum_i (Y_{j,i} - mean_j)^2, accumulated per term on the deviations from its first summand (exactly 0
  *   where the samples coincide, as at t = T);  out_se = sqrt(max(Var, 0)) in float32.
+ *   Where the unclipped u is NaN (a NaN in the root's row of x_t; quadrature rules whose tabulated nodes are not increasing) out_se is NaN too,
+ *   never 0 or a finite number.
  *   It is the Monte-Carlo error of the UNCLIPPED root sum: the clip of the returned u is not modelled, the Picard truncation bias is not
  *   included and, in ACCUMULATE, neither is the surrogate's own error (u_hat is deterministic given the fit: se(u_hat + u) = se(u)).
  * SCASML_ERR_UNSUPPORTED (scasml_last_error names the cause): rng.world != 1 (sample-sharded units split a path's addends across ranks:

@@ -105,6 +105,7 @@ class PicardOracle:
         self.sigma, self.mu = eq.sigma(), eq.mu()
         self.clip = eq.uncertainty if gp is not None else eq.norm_estimation
         self.sites_executed = 0
+        self._rec = None                             # root_summands: the root call's summands, recorded beside the unchanged sums
 
     # reference call surface -------------------------------------------------
     def uz_solve(self, n, par, x_t, root0=0, rank=0, world=1, owner=None):
@@ -128,6 +129,20 @@ class PicardOracle:
             if self.variant == "quad":               # the full-history solvers draw everything from the one terminal key
                 self.jax_splits += self._jax_splits_in_call(n)
         return self._uz(n, x_t[:, :-1].copy(), x_t[:, -1].copy(), roots, 0, top=True, cbase=0, jx=jx)
+
+    def root_summands(self, n, par, x_t, root0=0):
+        """The summands Y_{j,i} of the ROOT call (include/scasml_hip.h, scasml_picard_tree_stderr) from ONE walk of the tree:
+        ``[Y_g, Y_0, ..., Y_{n-1}]``, float64 arrays of shape (N_j, B).  Y_g[m] = g(X_T^m) / mg ((g - u_hat) / mg with a surrogate);
+        Y_l[m] is what sample path m of level l adds to u: over its q nodes the "+" addend, the "-" addend (l > 0) and the residual addend
+        (l = 0, with a surrogate), each with its 1 / mc.  Their total is the unclipped u.  Philox stream, one rank, no compat flags."""
+        if self.jax_stream or self.compat_crn or self.compat_f16:
+            raise ValueError("root_summands: the Philox stream without compat flags only (CRN shares draws between summands)")
+        self._rec = []
+        try:
+            self.uz_solve(n, par, x_t, root0=root0)
+            return [np.stack(Y) for Y in self._rec]
+        finally:
+            self._rec = None
 
     def uz_call(self, level, par, x_t, root0=0, base=0):
         """(u, z) of ONE inner call of the recursion on the Philox stream: the level-``level`` call whose first RNG site is ``base``, started at
@@ -220,6 +235,13 @@ class PicardOracle:
         out = np.clip(out, -c, c)
         return out if (self.variant == "fh" and self.gp is not None) else self._h(out)
 
+    def _new_term(self, top):
+        """root_summands: the list that takes the next term's summands (None unless recording, and in the root call only)."""
+        if not top or self._rec is None:
+            return None
+        self._rec.append([])
+        return self._rec[-1]
+
     def _uz(self, n, x, t, roots, base, top=False, cbase=None, jx=None):
         """base: first RNG site of this call's subtree.  cbase: where the call's TERMINAL draws
         come from -- equal to base except under compat_crn, where it is the base the call
@@ -236,6 +258,7 @@ class PicardOracle:
         tau = T - t
         su = np.zeros(x.shape[0])
         sz = np.zeros((x.shape[0], d))
+        rec = self._new_term(top)
         for m in range(mg):                          # MLP.py:175-202
             if not self._owned(top, m):
                 continue
@@ -249,6 +272,8 @@ class PicardOracle:
             su += G
             sz += G[:, None] * N
             self.sites_executed += 1
+            if rec is not None:
+                rec.append(G / mg)
         with np.errstate(all="ignore"):
             return su / mg, sz / (mg * (tau + eps))[:, None]
 
@@ -284,7 +309,9 @@ class PicardOracle:
             if jx is not None and l:
                 lp = l - 1                           # nodes of the previous level: q_prev x (1 + children's sub-keys)
                 jsplit += int(Q[rho - 1, n - lp - 1]) * (1 + self._jax_splits_in_call(lp) + (self._jax_splits_in_call(lp - 1) if lp else 0))
+            rec = self._new_term(top)
             for m in range(mc):
+                ym = np.zeros(x.shape[0])            # root_summands: what this sample path adds to u
                 X = x.copy()
                 W = np.zeros_like(x)
                 o_k0 = o                             # offsets of this path's k=0 children (compat_crn)
@@ -321,6 +348,7 @@ class PicardOracle:
                         sim = self._uz(l, X, tk, roots, base + o, cbase=cbase + o_k0 + 1, jx=kid)
                         y = self._f(X, tk, sim[:, 0], sim[:, 1:])
                         u = u + wloc[:, k] * y / mc                              # MLP.py:248
+                        ym = ym + wloc[:, k] * y / mc
                         z = z + (wloc[:, k] * y)[:, None] * W / (mc * dplus[k])[:, None]   # MLP.py:249
                     o += s_l
                     if l:
@@ -328,13 +356,17 @@ class PicardOracle:
                             sim = self._uz(l - 1, X, tk, roots, base + o, cbase=cbase + o_k0 + 1 + s_l, jx=kid2)
                             y = self._f(X, tk, sim[:, 0], sim[:, 1:])
                             u = u - wloc[:, k] * y / mc                          # MLP.py:269
+                            ym = ym - wloc[:, k] * y / mc
                             z = z - (wloc[:, k] * y)[:, None] * W / (mc * dminus[k])[:, None]  # MLP.py:271
                         o += s_lm
                     elif self.gp is not None:                                # ScaSML.py:274-280
                         P = np.concatenate([X, tk[:, None]], axis=1)
                         eps = self.gp.compute_PDE_loss(P)[:, 0]
                         u = u + wloc[:, k] * eps / mc
+                        ym = ym + wloc[:, k] * eps / mc
                         z = z + (wloc[:, k] * eps)[:, None] * W / (mc * dminus[k])[:, None]
+                if rec is not None:
+                    rec.append(ym)
         return self._finish(u, z, top)
 
     def _uz_fh(self, n, x, t, roots, base, top, cbase, jx=None):
@@ -348,7 +380,9 @@ class PicardOracle:
             mc = M ** (n - l)                                     # MLP_full_history.py:132
             s_l = site_count("fh", l, M)
             s_lm = site_count("fh", l - 1, M) if l else 0
+            rec = self._new_term(top)
             for m in range(mc):
+                ym = np.zeros(x.shape[0])                          # root_summands: what this sample adds to u
                 owned = self._owned(top, unit)                     # the "+" addend of this (single-node) sample; "-" below for l > 0
                 unit += 1
                 owned_minus = False
@@ -380,6 +414,7 @@ class PicardOracle:
                     sim = self._uz(l, X, tk, roots, base + o, jx=kid)
                     y = self._f(X, tk, sim[:, 0], sim[:, 1:])
                     u = u + tau * y / mc                               # :157
+                    ym = ym + tau * y / mc
                     z = z + (tau * y)[:, None] * wgt / mc
                 o += s_l
                 if l:
@@ -387,11 +422,15 @@ class PicardOracle:
                         sim = self._uz(l - 1, X, tk, roots, base + o, jx=kid)
                         y = self._f(X, tk, sim[:, 0], sim[:, 1:])
                         u = u - tau * y / mc                           # :175
+                        ym = ym - tau * y / mc
                         z = z - (tau * y)[:, None] * wgt / mc
                     o += s_lm
                 elif self.gp is not None:                          # ScaSML_full_history.py:189-195
                     P = np.concatenate([X, tk[:, None]], axis=1)
                     eps = self.gp.compute_PDE_loss(P)[:, 0]
                     u = u + tau * eps / mc
+                    ym = ym + tau * eps / mc
                     z = z + (tau * eps)[:, None] * wgt / mc
+                if rec is not None:
+                    rec.append(ym)
         return self._finish(u, z, top)

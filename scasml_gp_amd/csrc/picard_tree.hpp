@@ -602,7 +602,8 @@ __global__ __launch_bounds__(256) void picard_tree_kernel(const TreeArgs a) {
                 if constexpr (MODE == SCASML_MODE_ACCUMULATE) {
                     if (a.out_uhat) a.out_uhat[local] = w.gp_at((uint32_t)(a.ppr - 1)).x;
                 }
-                if constexpr (SE) a.out_se[local] = sqrtf(fmaxf(w.se.var, 0.0f));
+                // Var <= 0 (rounding) gives 0; a NaN Var -- the root's u is NaN -- stays NaN (fmaxf would turn it into an exact-looking 0)
+                if constexpr (SE) a.out_se[local] = w.se.var <= 0.0f ? 0.0f : sqrtf(w.se.var);
             }
             if (dim0 + 0 < a.d) out[1 + dim0 + 0] = z.x;
             if (dim0 + 1 < a.d) out[1 + dim0 + 1] = z.y;

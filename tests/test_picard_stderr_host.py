@@ -109,3 +109,71 @@ def test_standard_error_instances_stay_inside_the_plain_scratch_and_loop_figures
     assert all(seen[(1, mode, 5, eq)][0] == 0 and not seen[(1, mode, 5, eq)][2] for mode in (MODE_MLP, MODE_ACCUMULATE) for eq in (0, 1))
     for key in sorted(k for k in seen if k[0] == 0 and k[2] == 5):
         print("quadrature n = 5 (spills without the flag too): <%d, %d, 5, %d> scratch %d vgpr %d" % (key[0], key[1], key[3], seen[key][0], seen[key][1]))
+
+
+# ---- the oracle's one-walk summands (PicardOracle.root_summands) and the rounding bound of tests/test_gpu_stderr_sweep.py ----------------
+def _summand_oracle(variant, surrogate, d=6, seed=7, stream=3):
+    from oracle.equation import GradDependentNonlinear
+    from oracle.mlp import PicardOracle
+    from test_gpu_picard_sweep import _Surrogate
+    return PicardOracle(GradDependentNonlinear(d + 1), variant, gp=_Surrogate(d) if surrogate else None, seed=seed, stream=stream)
+
+
+@pytest.mark.parametrize("surrogate", [False, True], ids=["mlp", "surrogate"])
+@pytest.mark.parametrize("variant,n,par", [("quad", 2, 3), ("quad", 3, 3), ("fh", 2, 3), ("fh", 3, 2)])
+def test_root_summands_are_the_owner_mask_summands_from_one_walk(variant, n, par, surrogate):
+    """Summand by summand against uz_solve(..., world=2, owner=...) with one summand's units marked (one walk per summand), to 1e-15; the
+    summands add up to the unclipped u of a two-rank solve summed over its ranks; uz_solve itself is undisturbed by the recording."""
+    import numpy as np
+    from test_gpu_picard_stderr import _groups
+    from test_gpu_picard_sweep import _points
+    d, B = 6, 3
+    xt = _points(d, B, 77)
+    ora = _summand_oracle(variant, surrogate)
+    before = ora.uz_solve(n, par, xt)
+    Ys = ora.root_summands(n, par, xt)
+    assert ora._rec is None and np.array_equal(ora.uz_solve(n, par, xt), before, equal_nan=True)
+    groups, units = _groups(variant, n, par)
+    assert [Y.shape for Y in Ys] == [(N, B) for N, _ in groups] and all(Y.dtype == np.float64 for Y in Ys)
+    for Y, (N, summands) in zip(Ys, groups):
+        for i, mine in enumerate(summands):
+            owner = np.ones(units, dtype=np.uint8)
+            owner[mine] = 0
+            want = ora.uz_solve(n, par, xt, rank=0, world=2, owner=owner)[:, 0]
+            assert np.abs(Y[i] - want).max() <= 1e-15, (N, i, np.abs(Y[i] - want).max())
+    u = sum(ora.uz_solve(n, par, xt, rank=r, world=2)[:, 0] for r in range(2))
+    total = sum(Y.sum(axis=0) for Y in Ys)
+    assert np.abs(total - u).max() <= 1e-14 * max(1.0, np.abs(u).max())     # the same addends in another order
+    # a wrapped root counter reaches the summands as it reaches uz_solve
+    Yw = ora.root_summands(n, par, xt, root0=(1 << 32) - 1)
+    assert np.abs(Yw[0][:, 1:] - ora.root_summands(n, par, xt[1:])[0]).max() == 0.0
+
+
+def test_root_summands_refuses_the_parity_modes():
+    import numpy as np
+    from oracle.equation import GradDependentNonlinear
+    from oracle.mlp import PicardOracle
+    xt = np.zeros((1, 7))
+    for kw in (dict(compat_crn=True), dict(compat_f16=True), dict(jax_stream=True)):
+        with pytest.raises(ValueError):
+            PicardOracle(GradDependentNonlinear(7), "quad", seed=1, **kw).root_summands(2, 3, xt)
+
+
+@pytest.mark.parametrize("surrogate", [False, True], ids=["mlp", "surrogate"])
+@pytest.mark.parametrize("variant,n,par", [("quad", 3, 3), ("fh", 3, 2), ("fh", 4, 2)])
+def test_a_float32_emulation_of_the_accumulation_stays_inside_the_derived_bound(variant, n, par, surrogate):
+    """B_var of tests/test_gpu_stderr_sweep.py (check (b)) against a float32 emulation of SeTerm on the oracle's summands rounded to float32:
+    the emulation stays inside the bound (it is not too tight) and the bound is a few 1e-6 of Var (it is not vacuous)."""
+    import numpy as np
+    from test_gpu_picard_sweep import _points
+    from test_gpu_stderr_sweep import emulate_float32, se_stats
+    xt = _points(6, 16, 78)
+    Ys = [Y.astype(np.float32).astype(np.float64) for Y in _summand_oracle(variant, surrogate).root_summands(n, par, xt)]
+    st = se_stats(Ys)
+    err = np.abs(emulate_float32(Ys).astype(np.float64) - st["var"])
+    print("%s n=%d: |Var32 - Var64| / Var %.1e..%.1e, B_var / Var %.1e..%.1e" % (variant, n, (err / st["var"]).min(), (err / st["var"]).max(),
+                                                                                (st["b_var"] / st["var"]).min(), (st["b_var"] / st["var"]).max()))
+    assert np.all(st["var"] > 0) and np.all(err <= st["b_var"])
+    assert np.all(st["b_var"] <= 1e-4 * st["var"])
+    # and of se: the whole bound of check (b) is below 1e-4 of se, a hundredth of what check (a) allows
+    assert np.all(st["bound_b"] <= 1e-4 * st["se"])
