@@ -7,7 +7,7 @@
 // An equation is one specialisation of EqDef below; everything else -- the Picard kernels' f and g, the PDE residual of the
 // GP evaluation (models/GP.py:746-769), the collocation operator F and its derivatives in the Newton kernels (:705-743) --
 // is generated from it.  To add an equation: add an id to include/scasml_hip.h, a specialisation here, a case to
-// SCASML_EQ_SWITCH, and its Python twin in scasml_gp_amd/equations/equations.py (host view) and oracle/equation.py (checker).
+// launch_equation (picard_tree.hpp) and to eq_f / eq_parts below, and its Python twin in scasml_gp_amd/equations/equations.py (host view) and oracle/equation.py (checker).
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -89,14 +89,6 @@ struct EqDef<SCASML_EQ_QUADRATIC_GRADIENT_REACTION_DIFFUSION> {
 // equations every kernel family covers (Picard tree in all modes, GP training, fused evaluation) / those of the surrogate-free Picard tree alone
 inline bool eq_mlp_only(int eq_id) { return eq_id == SCASML_EQ_QUADRATIC_GRADIENT_REACTION_DIFFUSION; }
 inline bool eq_known(int eq_id) { return eq_id == SCASML_EQ_GRAD_DEPENDENT_NONLINEAR || eq_id == SCASML_EQ_CUBIC_REACTION_DIFFUSION; }
-
-// run `stmt` with EQ bound to the compile-time id
-#define SCASML_EQ_SWITCH(eq_id, stmt)                                                              \
-    switch (eq_id) {                                                                               \
-        case SCASML_EQ_GRAD_DEPENDENT_NONLINEAR: { constexpr int EQ = SCASML_EQ_GRAD_DEPENDENT_NONLINEAR; stmt; } break; \
-        case SCASML_EQ_CUBIC_REACTION_DIFFUSION: { constexpr int EQ = SCASML_EQ_CUBIC_REACTION_DIFFUSION; stmt; } break; \
-        default: break;                                                                            \
-    }
 
 // f(u, s) by runtime id (once-per-point uses: the PDE residual at the end of the GP evaluation)
 template <class T>

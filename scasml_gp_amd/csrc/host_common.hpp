@@ -1,4 +1,5 @@
-// Host-only helpers of libscasml_hip.so that need no HIP header: the thread-local error string and fail().
+// Host-only helpers of libscasml_hip.so that need no HIP header: the thread-local error string and fail(), the argument checks the Picard entry
+// points share, and the tile order of the FP64 update kernels.
 // plan_host.cpp (plain C++, also built with -fsanitize=address,undefined by tests/test_host_sanitizers.py) includes only this.
 #pragma once
 #include <math.h>
@@ -18,6 +19,26 @@ inline int fail(int code, const char *fmt, ...) {
     vsnprintf(error_buffer(), 512, fmt, ap);
     va_end(ap);
     return code;
+}
+
+// The checks scasml_picard_tree and scasml_picard_stage both open with, in this order (what follows them differs: the tree answers an empty
+// batch next, the stage only after it has looked at everything else).  `who` prefixes the message.
+inline int check_batch(const char *who, const void *prob, const void *plan, int64_t B, int64_t site_stride) {
+    if (!prob || !plan) return fail(SCASML_ERR_ARG, "%s: null argument", who);
+    if (B < 0) return fail(SCASML_ERR_ARG, "%s: negative batch", who);
+    if (site_stride != 0 && site_stride < B) return fail(SCASML_ERR_ARG, "%s: site_stride %lld is smaller than the batch %lld", who, (long long)site_stride, (long long)B);
+    return 0;
+}
+
+// The first term [np][l] of a plan's levels 1 .. n that no walk can take (a path of no or too many nodes, no sample); false: every term is fine.
+// plan.n must already be known to lie in 0 .. SCASML_MAX_LEVEL.
+inline bool first_bad_term(const scasml_plan &plan, int &np, int &l) {
+    for (np = 1; np <= plan.n; ++np)
+        for (l = 0; l < np; ++l) {
+            const scasml_term &t = plan.term[np][l];
+            if (t.q < 1 || t.q > SCASML_MAX_Q || t.mc < 1) return true;
+        }
+    return false;
 }
 
 // host + device where the HIP compiler sees it (the kernels' tile order), plain host code in plan_host.cpp (scasml_tile_order: the CPU tests)

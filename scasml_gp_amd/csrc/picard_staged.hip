@@ -45,8 +45,7 @@ __global__ __launch_bounds__(256) void picard_stage_kernel(const StageArgs a) {
     const uint32_t root = a.root0 + (uint32_t)local;
     const int dim0 = 4 * (int)gl;
     const bool row_lane = dim0 < a.kp;
-    const float4 mask = make_float4(dim0 + 0 < a.d ? 1.0f : 0.0f, dim0 + 1 < a.d ? 1.0f : 0.0f, dim0 + 2 < a.d ? 1.0f : 0.0f,
-                                    dim0 + 3 < a.d ? 1.0f : 0.0f);
+    const float4 mask = live_mask(dim0, a.d);
     // site-major rows: the site's block starts at a wave-uniform 64-bit base, the lane adds a 32-bit offset (site_stride * kp < 2^32)
     const int64_t block = a.Bs * a.kp;
     const uint32_t off4 = (uint32_t)((local * a.kp + (row_lane ? dim0 : 0)) >> 2);
@@ -117,7 +116,7 @@ __global__ __launch_bounds__(256) void picard_stage_kernel(const StageArgs a) {
         }
     }
     u = clip1(u, a.clip);                                                  // MLP.py:272-274, NaN kept
-    z = make_float4(clip1(z.x, a.clip), clip1(z.y, a.clip), clip1(z.z, a.clip), clip1(z.w, a.clip));
+    z = clip4(z, a.clip);
     if (!valid) return;
     if (S < a.plan.n) {
         if (!row_lane) return;
@@ -128,10 +127,7 @@ __global__ __launch_bounds__(256) void picard_stage_kernel(const StageArgs a) {
     } else {
         float *out = a.out + local * (a.d + 1);
         if (gl == 0) out[0] = u;
-        if (dim0 + 0 < a.d) out[1 + dim0 + 0] = z.x;
-        if (dim0 + 1 < a.d) out[1 + dim0 + 1] = z.y;
-        if (dim0 + 2 < a.d) out[1 + dim0 + 2] = z.z;
-        if (dim0 + 3 < a.d) out[1 + dim0 + 3] = z.w;
+        store_z(out, dim0, a.d, z);
     }
 }
 
@@ -142,9 +138,7 @@ using namespace scasml;
 extern "C" int scasml_picard_stage(const scasml_problem *prob, const scasml_plan *plan, int32_t stage, const int32_t *entries, int64_t n_entries,
                                    int64_t B, int64_t site_stride, scasml_rng rng, const float *points, const float *values, float *uz,
                                    float *out_uz, void *stream) {
-    if (!prob || !plan) return fail(SCASML_ERR_ARG, "picard_stage: null argument");
-    if (B < 0) return fail(SCASML_ERR_ARG, "picard_stage: negative batch");
-    if (site_stride != 0 && site_stride < B) return fail(SCASML_ERR_ARG, "picard_stage: site_stride %lld is smaller than the batch %lld", (long long)site_stride, (long long)B);
+    if (const int rc = check_batch("picard_stage", prob, plan, B, site_stride)) return rc;
     if (prob->d < 1 || prob->d > SCASML_MAX_DIM) return fail(SCASML_ERR_UNSUPPORTED, "picard_stage: d=%d outside 1..%d", prob->d, SCASML_MAX_DIM);
     if (plan->variant != 0 && plan->variant != 1) return fail(SCASML_ERR_ARG, "picard_stage: variant %d", plan->variant);
     if (plan->n < 1 || plan->n > SCASML_MAX_LEVEL) return fail(SCASML_ERR_UNSUPPORTED, "picard_stage: level n=%d outside 1..%d", plan->n, SCASML_MAX_LEVEL);
@@ -152,41 +146,21 @@ extern "C" int scasml_picard_stage(const scasml_problem *prob, const scasml_plan
     if (rng.flags != 0) return fail(SCASML_ERR_UNSUPPORTED, "picard_stage: rng.flags 0x%x: the staged path runs on the Philox stream only", rng.flags);
     if (rng.world != 1 || rng.rank != 0) return fail(SCASML_ERR_UNSUPPORTED, "picard_stage: sample sharding (world %d) is not supported", rng.world);
     if (n_entries < 1 || !entries) return fail(SCASML_ERR_ARG, "picard_stage: no subtree entries");
-    for (int np = 1; np <= plan->n; ++np)
-        for (int l = 0; l < np; ++l) {
-            const scasml_term &t = plan->term[np][l];
-            if (t.q < 1 || t.q > SCASML_MAX_Q || t.mc < 1) return fail(SCASML_ERR_ARG, "picard_stage: bad term [%d][%d]", np, l);
-        }
+    int np, l;
+    if (first_bad_term(*plan, np, l)) return fail(SCASML_ERR_ARG, "picard_stage: bad term [%d][%d]", np, l);
     if (B == 0) return 0;
     if (!points || !values) return fail(SCASML_ERR_ARG, "picard_stage: points and values are required");
     if (stage < plan->n ? !uz : !out_uz) return fail(SCASML_ERR_ARG, "picard_stage: stage %d of %d needs %s", stage, plan->n, stage < plan->n ? "uz" : "out_uz");
     StageArgs a;
-    a.plan = *plan;
+    const int rpw = fill_common_args(a, prob, plan, rng, B, site_stride);
     a.points = points;
     a.vals = reinterpret_cast<const float2 *>(values);
     a.entries = reinterpret_cast<const int2 *>(entries);
     a.uz = uz;
     a.out = out_uz;
-    a.B = B;
-    a.Bs = site_stride ? site_stride : B;
-    a.ppr = (int64_t)plan->sites[plan->n] + 1;
     a.n_entries = n_entries;
-    a.k0 = (uint32_t)(rng.seed & 0xFFFFFFFFu);
-    a.k1 = (uint32_t)(rng.seed >> 32);
-    a.stream = rng.stream;
-    a.root0 = rng.root0;
     a.S = stage;
-    a.d = prob->d;
-    a.kp = scasml_point_stride(prob->d);
     if (a.Bs * a.kp >= ((int64_t)1 << 32)) return fail(SCASML_ERR_UNSUPPORTED, "picard_stage: site_stride %lld too large for 32-bit row offsets", (long long)a.Bs);
-    a.G = ceil_pow2(a.kp / 4);
-    a.logG = 0;
-    while ((1 << a.logG) < a.G) ++a.logG;
-    a.T = prob->T;
-    a.mu = prob->mu;
-    a.sigma = prob->sigma;
-    a.clip = prob->clip;
-    const int rpw = 64 / a.G;
     a.groups = (B + rpw - 1) / rpw;
     const int64_t blocks = (n_entries * a.groups + 3) / 4;
     if (blocks > 0x7FFFFFFF) return fail(SCASML_ERR_UNSUPPORTED, "picard_stage: batch too large");

@@ -22,35 +22,6 @@
 
 namespace scasml {
 
-template <int VAR, int MODE, int EQ>
-static int launch_level(const TreeArgs &a, int n, dim3 grid, hipStream_t s) {
-    switch (n) {
-        case 1: hipLaunchKernelGGL((picard_tree_kernel<VAR, MODE, 1, EQ>), grid, dim3(256), 0, s, a); break;
-        case 2: hipLaunchKernelGGL((picard_tree_kernel<VAR, MODE, 2, EQ>), grid, dim3(256), 0, s, a); break;
-        case 3: hipLaunchKernelGGL((picard_tree_kernel<VAR, MODE, 3, EQ>), grid, dim3(256), 0, s, a); break;
-        case 4: hipLaunchKernelGGL((picard_tree_kernel<VAR, MODE, 4, EQ>), grid, dim3(256), 0, s, a); break;
-        case 5: hipLaunchKernelGGL((picard_tree_kernel<VAR, MODE, 5, EQ>), grid, dim3(256), 0, s, a); break;
-        default: return fail(SCASML_ERR_UNSUPPORTED, "picard_tree: level n=%d outside 1..%d", n, SCASML_MAX_LEVEL);
-    }
-    return check_launch("picard_tree launch");
-}
-
-template <int VAR, int EQ>
-static int launch_mode(const TreeArgs &a, int mode, int n, dim3 grid, hipStream_t s) {
-    if (a.jk) {   // the reference's own random stream: instantiated in translation units of their own (picard_tree.hpp)
-        if (mode != SCASML_MODE_MLP && mode != SCASML_MODE_GENERATE && mode != SCASML_MODE_ACCUMULATE) return fail(SCASML_ERR_ARG, "picard_tree: unknown mode %d", mode);
-        if (n < 1 || n > SCASML_MAX_LEVEL) return fail(SCASML_ERR_UNSUPPORTED, "picard_tree: level n=%d outside 1..%d", n, SCASML_MAX_LEVEL);
-        return n <= 3 ? launch_tree_jax(a, VAR, mode, EQ, n, grid, s) : launch_tree_jax_deep(a, VAR, mode, EQ, n, grid, s);
-    }
-    switch (mode) {
-        case SCASML_MODE_MLP: return launch_level<VAR, SCASML_MODE_MLP, EQ>(a, n, grid, s);
-        // GENERATE evaluates neither f nor g: one instantiation (equation 0) serves every equation
-        case SCASML_MODE_GENERATE: return launch_level<VAR, SCASML_MODE_GENERATE, SCASML_EQ_GRAD_DEPENDENT_NONLINEAR>(a, n, grid, s);
-        case SCASML_MODE_ACCUMULATE: return launch_level<VAR, SCASML_MODE_ACCUMULATE, EQ>(a, n, grid, s);
-    }
-    return fail(SCASML_ERR_ARG, "picard_tree: unknown mode %d", mode);
-}
-
 __global__ void clip_kernel(float *v, int64_t n, float c, int round16) {
     const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (i < n) {
@@ -81,9 +52,7 @@ __global__ void debug_jax_normals_kernel(uint32_t k0, uint32_t k1, uint64_t inde
 
 int picard_tree_run(const scasml_problem *prob, const scasml_plan *plan, int mode, const float *x_t, int64_t B, int64_t site_stride, scasml_rng rng,
                     float *points, const float *gp_vals, float *out_uz, float *out_uhat, float *out_se, bool want_se, void *stream) {
-    if (!prob || !plan) return fail(SCASML_ERR_ARG, "picard_tree: null argument");
-    if (B < 0) return fail(SCASML_ERR_ARG, "picard_tree: negative batch");
-    if (site_stride != 0 && site_stride < B) return fail(SCASML_ERR_ARG, "picard_tree: site_stride %lld is smaller than the batch %lld", (long long)site_stride, (long long)B);
+    if (const int rc = check_batch("picard_tree", prob, plan, B, site_stride)) return rc;
     if (B == 0) return 0;
     if (!x_t) return fail(SCASML_ERR_ARG, "picard_tree: x_t is null");
     if (prob->d < 1 || prob->d > SCASML_MAX_DIM)
@@ -99,11 +68,8 @@ int picard_tree_run(const scasml_problem *prob, const scasml_plan *plan, int mod
     if (mode == SCASML_MODE_ACCUMULATE && (!gp_vals || !points))
         return fail(SCASML_ERR_ARG, "picard_tree: ACCUMULATE needs gp_vals and the points emitted by GENERATE");
     if (mode != SCASML_MODE_GENERATE && !out_uz) return fail(SCASML_ERR_ARG, "picard_tree: out_uz is null");
-    for (int np = 1; np <= plan->n; ++np)
-        for (int l = 0; l < np; ++l) {
-            const scasml_term &t = plan->term[np][l];
-            if (t.q < 1 || t.q > SCASML_MAX_Q || t.mc < 1) return fail(SCASML_ERR_ARG, "picard_tree: bad term [%d][%d]", np, l);
-        }
+    int np, lp;
+    if (first_bad_term(*plan, np, lp)) return fail(SCASML_ERR_ARG, "picard_tree: bad term [%d][%d]", np, lp);
     if (want_se) {   // scasml_picard_tree_stderr: what has no estimate is refused, never answered with a partial number
         if (mode != SCASML_MODE_MLP && mode != SCASML_MODE_ACCUMULATE)
             return fail(SCASML_ERR_ARG, "picard_tree_stderr: mode %d has no estimate (SCASML_MODE_MLP or SCASML_MODE_ACCUMULATE)", mode);
@@ -129,20 +95,13 @@ int picard_tree_run(const scasml_problem *prob, const scasml_plan *plan, int mod
         return 0;
     }
     TreeArgs a;
-    a.plan = *plan;
+    const int rpw = fill_common_args(a, prob, plan, rng, B, site_stride);
     a.x_t = x_t;
     a.points = points;
     a.gpv = reinterpret_cast<const float4 *>(gp_vals);
     a.out_uz = out_uz;
     a.out_uhat = out_uhat;
     a.out_se = want_se ? out_se : nullptr;
-    a.B = B;
-    a.Bs = site_stride ? site_stride : B;
-    a.ppr = (int64_t)plan->sites[plan->n] + 1;
-    a.k0 = (uint32_t)(rng.seed & 0xFFFFFFFFu);
-    a.k1 = (uint32_t)(rng.seed >> 32);
-    a.stream = rng.stream;
-    a.root0 = rng.root0;
     a.rank = rng.rank;
     a.world = rng.world;
     a.owner = rng.world > 1 ? rng.unit_owner : nullptr;
@@ -150,31 +109,15 @@ int picard_tree_run(const scasml_problem *prob, const scasml_plan *plan, int mod
     a.f16 = (rng.flags & SCASML_RNG_COMPAT_F16) ? 1 : 0;
     a.jk = (rng.flags & SCASML_RNG_JAX_STREAM) ? rng.jax_keys : nullptr;
     if ((rng.flags & SCASML_RNG_JAX_STREAM) && !rng.jax_keys) return fail(SCASML_ERR_ARG, "picard_tree: SCASML_RNG_JAX_STREAM needs scasml_rng.jax_keys");
-    a.d = prob->d;
-    a.kp = scasml_point_stride(prob->d);
-    a.G = ceil_pow2(a.kp / 4);
-    a.logG = 0;
-    while ((1 << a.logG) < a.G) ++a.logG;
-    a.T = prob->T;
-    a.mu = prob->mu;
-    a.sigma = prob->sigma;
-    a.clip = prob->clip;
-    const int rpw = 64 / a.G;
     const int64_t waves = mode == SCASML_MODE_GENERATE ? (B * (a.kp / 4) + 63) / 64 : (B + rpw - 1) / rpw;   // GENERATE: flat (root, quad) lanes
     const int64_t blocks = (waves + 3) / 4;
     if (blocks > 0x7FFFFFFF) return fail(SCASML_ERR_UNSUPPORTED, "picard_tree: batch too large");
     const dim3 grid((unsigned)blocks);
-    if (want_se) {   // instantiated in translation units of their own (picard_tree.hpp)
-        if (plan->n > 3) return launch_tree_stderr_deep(a, plan->variant, mode, prob->eq_id, plan->n, grid, s);
-        return launch_tree_stderr(a, plan->variant, mode, prob->eq_id, plan->n, grid, s);
-    }
-    if (eq_mlp_only(prob->eq_id)) {
-        constexpr int EQ2 = SCASML_EQ_QUADRATIC_GRADIENT_REACTION_DIFFUSION;
-        return plan->variant == 0 ? launch_level<0, SCASML_MODE_MLP, EQ2>(a, plan->n, grid, s) : launch_level<1, SCASML_MODE_MLP, EQ2>(a, plan->n, grid, s);
-    }
-    int rc = SCASML_ERR_UNSUPPORTED;
-    SCASML_EQ_SWITCH(prob->eq_id, rc = (plan->variant == 0 ? launch_mode<0, EQ>(a, mode, plan->n, grid, s) : launch_mode<1, EQ>(a, mode, plan->n, grid, s)));
-    return rc;
+    // the ladder (picard_tree.hpp) of the unit that holds the kernels: standard errors and the reference's stream have two units each
+    const int v = plan->variant, eq = prob->eq_id, n = plan->n;
+    if (want_se) return n > 3 ? launch_tree_stderr_deep(a, v, mode, eq, n, grid, s) : launch_tree_stderr(a, v, mode, eq, n, grid, s);
+    if (a.jk) return n > 3 ? launch_tree_jax_deep(a, v, mode, eq, n, grid, s) : launch_tree_jax(a, v, mode, eq, n, grid, s);
+    return launch_tree<false, false, 1, SCASML_MAX_LEVEL>(a, v, mode, eq, n, grid, s);
 }
 
 }  // namespace scasml

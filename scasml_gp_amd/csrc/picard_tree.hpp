@@ -1,7 +1,11 @@
-// Picard-tree walker and kernel template, shared by the translation units that instantiate it (picard_tree.hip: the Philox stream,
-// picard_tree_jax.hip / picard_tree_jax_deep.hip: the reference's own stream, SCASML_RNG_JAX_STREAM; picard_tree_stderr.hip /
-// picard_tree_stderr_deep.hip: the kernels that also estimate the standard error of u) -- split so that the build compiles
-// the instantiations in parallel (the JAX-stream kernels inline one Threefry + erf_inv per normal at every site of the unrolled tree).
+// Picard-tree walker (Walker), kernel template (picard_tree_kernel) and launch ladder (launch_tree: which instantiations exist, and the
+// variant / mode / equation / level selection among them), shared by the translation units that instantiate them:
+//   picard_tree.hip                                        the Philox stream, levels 1..5; the entry points' validation (picard_tree_run)
+//   picard_tree_jax.hip / picard_tree_jax_deep.hip         the reference's own stream (SCASML_RNG_JAX_STREAM, compat_rng = "jax"), levels 1..3 / 4, 5
+//   picard_tree_stderr.hip / picard_tree_stderr_deep.hip   the kernels that also estimate the standard error of u, levels 1..3 / 4, 5
+//   picard_staged.hip                                      the staged walk (its own kernel; shares the lane helpers and the args filler below)
+// Each of the first five holds ONE call of launch_tree, whose <JAX, SE, N_LO, N_HI> decide what that unit compiles -- split so that the build
+// compiles the instantiations in parallel (the JAX-stream kernels inline one Threefry + erf_inv per normal at every site of the unrolled tree).
 #pragma once
 #include <string.h>
 #include "common.hpp"
@@ -39,6 +43,19 @@ __device__ __forceinline__ float4 add4(float4 a, float s) { return make_float4(a
 __device__ __forceinline__ float4 f4_scale(float4 a, float s) { return make_float4(a.x * s, a.y * s, a.z * s, a.w * s); }
 __device__ __forceinline__ float4 mul4(float4 a, float4 b) { return make_float4(a.x * b.x, a.y * b.y, a.z * b.z, a.w * b.w); }
 __device__ __forceinline__ float clip1(float v, float c) { return v < -c ? -c : (v > c ? c : v); }  // keeps NaN (jnp.clip)
+__device__ __forceinline__ float4 clip4(float4 v, float c) { return make_float4(clip1(v.x, c), clip1(v.y, c), clip1(v.z, c), clip1(v.w, c)); }
+// A lane holds spatial dims dim0 .. dim0 + 3 of every d-vector: 1 on those below d (live), 0 on padding
+__device__ __forceinline__ float4 live_mask(int dim0, int d) {
+    return make_float4(dim0 + 0 < d ? 1.0f : 0.0f, dim0 + 1 < d ? 1.0f : 0.0f, dim0 + 2 < d ? 1.0f : 0.0f, dim0 + 3 < d ? 1.0f : 0.0f);
+}
+// this lane's live dims of z into a root's out_uz row (u, z_1 .. z_d).  (u, which lane 0 of the group stores, stays with the callers: the
+// tree kernel writes u_hat and the standard error between the two, and stores that may alias keep their order)
+__device__ __forceinline__ void store_z(float *out, int dim0, int d, float4 z) {
+    if (dim0 + 0 < d) out[1 + dim0 + 0] = z.x;
+    if (dim0 + 1 < d) out[1 + dim0 + 1] = z.y;
+    if (dim0 + 2 < d) out[1 + dim0 + 2] = z.z;
+    if (dim0 + 3 < d) out[1 + dim0 + 3] = z.w;
+}
 __device__ __forceinline__ float r16(float v) { return (float)(_Float16)v; }                          // .astype(jnp.float16), RNE
 // Hardware reciprocal / square root / exp2 (<= 1 ulp) for the arithmetic that is NOT part of the bit-exact
 // RNG specification: the IEEE-correct expansions cost ~10 VALU instructions each and these kernels are
@@ -526,7 +543,7 @@ struct Walker {
             level<N, 0, TOP>(x, t, tau, base, cbase, o, u, z, jrow, jsplit);
             if (!(TOP && a.world > 1)) {                         // MLP.py:272-274
                 u = clip1(u, a.clip);
-                z = make_float4(clip1(z.x, a.clip), clip1(z.y, a.clip), clip1(z.z, a.clip), clip1(z.w, a.clip));
+                z = clip4(z, a.clip);
                 // jnp.clip(...).astype(jnp.float16): MLP.py:274, ScaSML.py:284, MLP_full_history.py:180 -- ScaSML_full_history.py:199 does not cast
                 if (a.f16 && !(VAR == 1 && MODE != SCASML_MODE_MLP)) {
                     u = r16(u);
@@ -573,8 +590,7 @@ __global__ __launch_bounds__(256) void picard_tree_kernel(const TreeArgs a) {
     w.local = local;
     w.unit = 0;
     const int dim0 = 4 * (int)w.gl;
-    w.mask = make_float4(dim0 + 0 < a.d ? 1.0f : 0.0f, dim0 + 1 < a.d ? 1.0f : 0.0f,
-                         dim0 + 2 < a.d ? 1.0f : 0.0f, dim0 + 3 < a.d ? 1.0f : 0.0f);
+    w.mask = live_mask(dim0, a.d);
     w.tmask = make_float4(dim0 + 0 == a.d ? 1.0f : 0.0f, dim0 + 1 == a.d ? 1.0f : 0.0f,
                           dim0 + 2 == a.d ? 1.0f : 0.0f, dim0 + 3 == a.d ? 1.0f : 0.0f);
     w.row_lane = dim0 < a.kp && (MODE != SCASML_MODE_GENERATE || valid);
@@ -605,20 +621,101 @@ __global__ __launch_bounds__(256) void picard_tree_kernel(const TreeArgs a) {
                 // Var <= 0 (rounding) gives 0; a NaN Var -- the root's u is NaN -- stays NaN (fmaxf would turn it into an exact-looking 0)
                 if constexpr (SE) a.out_se[local] = w.se.var <= 0.0f ? 0.0f : sqrtf(w.se.var);
             }
-            if (dim0 + 0 < a.d) out[1 + dim0 + 0] = z.x;
-            if (dim0 + 1 < a.d) out[1 + dim0 + 1] = z.y;
-            if (dim0 + 2 < a.d) out[1 + dim0 + 2] = z.z;
-            if (dim0 + 3 < a.d) out[1 + dim0 + 3] = z.w;
+            store_z(out, dim0, a.d, z);
         }
     }
 }
 
-// the reference's own random stream (compat_rng = "jax"): instantiated in picard_tree_jax.hip (n <= 3) and picard_tree_jax_deep.hip (n = 4, 5)
+// ---- the launch ladder ---------------------------------------------------------------------------
+// Which picard_tree_kernel<VAR, MODE, N, EQ, JAX, SE> exist, for either variant and every level of a unit's range -- the one statement of it:
+//   GENERATE evaluates neither f nor g, so one instantiation (equation 0) serves every equation, and it has no sum to take an error of;
+//   an f of |z|^2 needs the surrogate's full gradient per site, so its equation runs surrogate-free (SCASML_MODE_MLP), and it is not one of
+//   the reference's, so never on the reference's stream;
+//   standard errors are estimated on the Philox stream only (picard_tree_kernel's static_assert).
+template <int MODE, int EQ, bool JAX, bool SE>
+constexpr bool tree_instance() {
+    if (SE && JAX) return false;
+    if (MODE == SCASML_MODE_GENERATE) return EQ == SCASML_EQ_GRAD_DEPENDENT_NONLINEAR && !SE;
+    if (EqDef<EQ>::kGradSquare) return MODE == SCASML_MODE_MLP && !JAX;
+    return true;
+}
+
+// level n among N .. N_HI (a short compile-time recursion), then the launch
+template <int VAR, int MODE, int EQ, bool JAX, bool SE, int N, int N_HI>
+int launch_level(const TreeArgs &a, int n, dim3 grid, hipStream_t s) {
+    if constexpr (!tree_instance<MODE, EQ, JAX, SE>()) {
+        return fail(SCASML_ERR_UNSUPPORTED, "picard_tree: no kernel for mode %d of equation id %d%s%s", MODE, EQ, JAX ? " on the reference's stream" : "",
+                    SE ? " with standard errors" : "");
+    } else if constexpr (N > N_HI) {
+        if (n < 1 || n > SCASML_MAX_LEVEL) return fail(SCASML_ERR_UNSUPPORTED, "picard_tree: level n=%d outside 1..%d", n, SCASML_MAX_LEVEL);
+        return fail(SCASML_ERR_UNSUPPORTED, "%s level n=%d is not in this translation unit", SE ? "picard_tree_stderr:" : "picard_tree: SCASML_RNG_JAX_STREAM", n);
+    } else {
+        if (n == N) {
+            hipLaunchKernelGGL((picard_tree_kernel<VAR, MODE, N, EQ, JAX, SE>), grid, dim3(256), 0, s, a);
+            return check_launch(SE ? "picard_tree_stderr launch" : "picard_tree launch");
+        }
+        return launch_level<VAR, MODE, EQ, JAX, SE, N + 1, N_HI>(a, n, grid, s);
+    }
+}
+
+template <int VAR, int MODE, bool JAX, bool SE, int N_LO, int N_HI>
+int launch_equation(const TreeArgs &a, int eq_id, int n, dim3 grid, hipStream_t s) {
+    switch (MODE == SCASML_MODE_GENERATE ? SCASML_EQ_GRAD_DEPENDENT_NONLINEAR : eq_id) {   // the one redirection of GENERATE (tree_instance)
+        case SCASML_EQ_GRAD_DEPENDENT_NONLINEAR: return launch_level<VAR, MODE, SCASML_EQ_GRAD_DEPENDENT_NONLINEAR, JAX, SE, N_LO, N_HI>(a, n, grid, s);
+        case SCASML_EQ_CUBIC_REACTION_DIFFUSION: return launch_level<VAR, MODE, SCASML_EQ_CUBIC_REACTION_DIFFUSION, JAX, SE, N_LO, N_HI>(a, n, grid, s);
+        case SCASML_EQ_QUADRATIC_GRADIENT_REACTION_DIFFUSION:
+            return launch_level<VAR, MODE, SCASML_EQ_QUADRATIC_GRADIENT_REACTION_DIFFUSION, JAX, SE, N_LO, N_HI>(a, n, grid, s);
+    }
+    return fail(SCASML_ERR_UNSUPPORTED, "picard_tree: unknown equation id %d", eq_id);
+}
+
+template <int VAR, bool JAX, bool SE, int N_LO, int N_HI>
+int launch_mode(const TreeArgs &a, int mode, int eq_id, int n, dim3 grid, hipStream_t s) {
+    switch (mode) {
+        case SCASML_MODE_MLP: return launch_equation<VAR, SCASML_MODE_MLP, JAX, SE, N_LO, N_HI>(a, eq_id, n, grid, s);
+        case SCASML_MODE_GENERATE: return launch_equation<VAR, SCASML_MODE_GENERATE, JAX, SE, N_LO, N_HI>(a, eq_id, n, grid, s);
+        case SCASML_MODE_ACCUMULATE: return launch_equation<VAR, SCASML_MODE_ACCUMULATE, JAX, SE, N_LO, N_HI>(a, eq_id, n, grid, s);
+    }
+    return fail(SCASML_ERR_ARG, "picard_tree: unknown mode %d", mode);
+}
+
+// A translation unit's kernels are those of the ONE launch_tree<JAX, SE, N_LO, N_HI> it instantiates: every variant, mode and equation of
+// tree_instance at levels N_LO .. N_HI.  Refuses an unknown mode, then a level outside the unit's range; launches nothing it refuses.
+template <bool JAX, bool SE, int N_LO, int N_HI>
+int launch_tree(const TreeArgs &a, int variant, int mode, int eq_id, int n, dim3 grid, hipStream_t s) {
+    return variant == 0 ? launch_mode<0, JAX, SE, N_LO, N_HI>(a, mode, eq_id, n, grid, s) : launch_mode<1, JAX, SE, N_LO, N_HI>(a, mode, eq_id, n, grid, s);
+}
+
+// the reference's own random stream (compat_rng = "jax"): picard_tree_jax.hip (n <= 3) and picard_tree_jax_deep.hip (n = 4, 5)
 int launch_tree_jax(const TreeArgs &a, int variant, int mode, int eq_id, int n, dim3 grid, hipStream_t s);
 int launch_tree_jax_deep(const TreeArgs &a, int variant, int mode, int eq_id, int n, dim3 grid, hipStream_t s);
 // the kernels that also estimate the standard error of u (SE = true): picard_tree_stderr.hip (n <= 3) and picard_tree_stderr_deep.hip (n = 4, 5)
 int launch_tree_stderr(const TreeArgs &a, int variant, int mode, int eq_id, int n, dim3 grid, hipStream_t s);
 int launch_tree_stderr_deep(const TreeArgs &a, int variant, int mode, int eq_id, int n, dim3 grid, hipStream_t s);
+// The fields TreeArgs and StageArgs (picard_staged.hip) have in common: the plan, the batch and its site-major row geometry, the Philox key
+// and the problem's constants.  Returns the roots a wavefront holds, 64 / G, which sizes either grid.
+template <class Args>
+int fill_common_args(Args &a, const scasml_problem *prob, const scasml_plan *plan, const scasml_rng &rng, int64_t B, int64_t site_stride) {
+    a.plan = *plan;
+    a.B = B;
+    a.Bs = site_stride ? site_stride : B;
+    a.ppr = (int64_t)plan->sites[plan->n] + 1;
+    a.k0 = (uint32_t)(rng.seed & 0xFFFFFFFFu);
+    a.k1 = (uint32_t)(rng.seed >> 32);
+    a.stream = rng.stream;
+    a.root0 = rng.root0;
+    a.d = prob->d;
+    a.kp = scasml_point_stride(prob->d);
+    a.G = ceil_pow2(a.kp / 4);
+    a.logG = 0;
+    while ((1 << a.logG) < a.G) ++a.logG;
+    a.T = prob->T;
+    a.mu = prob->mu;
+    a.sigma = prob->sigma;
+    a.clip = prob->clip;
+    return 64 / a.G;
+}
+
 // scasml_picard_tree and scasml_picard_tree_stderr (out_se non-null selects the latter's kernels): one validation, one launch geometry
 int picard_tree_run(const scasml_problem *prob, const scasml_plan *plan, int mode, const float *x_t, int64_t B, int64_t site_stride, scasml_rng rng,
                     float *points, const float *gp_vals, float *out_uz, float *out_uhat, float *out_se, bool want_se, void *stream);

@@ -5,28 +5,8 @@
 
 namespace scasml {
 
-template <int VAR, int MODE, int EQ>
-static int stderr_level(const TreeArgs &a, int n, dim3 grid, hipStream_t s) {
-    switch (n) {
-        case 4: hipLaunchKernelGGL((picard_tree_kernel<VAR, MODE, 4, EQ, false, true>), grid, dim3(256), 0, s, a); break;
-        case 5: hipLaunchKernelGGL((picard_tree_kernel<VAR, MODE, 5, EQ, false, true>), grid, dim3(256), 0, s, a); break;
-        default: return fail(SCASML_ERR_UNSUPPORTED, "picard_tree_stderr: level n=%d is not in this translation unit", n);
-    }
-    return check_launch("picard_tree_stderr launch");
-}
-
-template <int VAR>
-static int stderr_variant(const TreeArgs &a, int mode, int eq_id, int n, dim3 grid, hipStream_t s) {
-    if (eq_mlp_only(eq_id))   // picard_tree_run has refused every other mode for it
-        return stderr_level<VAR, SCASML_MODE_MLP, SCASML_EQ_QUADRATIC_GRADIENT_REACTION_DIFFUSION>(a, n, grid, s);
-    int rc = SCASML_ERR_UNSUPPORTED;
-    SCASML_EQ_SWITCH(eq_id, rc = (mode == SCASML_MODE_MLP ? stderr_level<VAR, SCASML_MODE_MLP, EQ>(a, n, grid, s)
-                                                          : stderr_level<VAR, SCASML_MODE_ACCUMULATE, EQ>(a, n, grid, s)));
-    return rc;
-}
-
 int launch_tree_stderr_deep(const TreeArgs &a, int variant, int mode, int eq_id, int n, dim3 grid, hipStream_t s) {
-    return variant == 0 ? stderr_variant<0>(a, mode, eq_id, n, grid, s) : stderr_variant<1>(a, mode, eq_id, n, grid, s);
+    return launch_tree<false, true, 4, 5>(a, variant, mode, eq_id, n, grid, s);
 }
 
 }  // namespace scasml

@@ -257,10 +257,8 @@ extern "C" int64_t scasml_plan_stage_list(const scasml_plan *plan_h, int32_t kin
         return fail(SCASML_ERR_ARG, "plan_stage_list: unknown kind %d", kind);
     }
     if (capacity < 0) return fail(SCASML_ERR_ARG, "plan_stage_list: negative capacity");
-    for (int np = 1; np <= n; ++np)
-        for (int l = 0; l < np; ++l)
-            if (plan_h->term[np][l].q < 1 || plan_h->term[np][l].q > SCASML_MAX_Q || plan_h->term[np][l].mc < 1)
-                return fail(SCASML_ERR_ARG, "plan_stage_list: bad term [%d][%d]", np, l);
+    int np, l;
+    if (first_bad_term(*plan_h, np, l)) return fail(SCASML_ERR_ARG, "plan_stage_list: bad term [%d][%d]", np, l);
     // count first: the sites must agree with plan.sites before anything is written
     StageWalk w{plan_h, kind, stage, nullptr, 0, 0};
     if (w.rec(n, 0, plan_h->sites[n]) != plan_h->sites[n]) return fail(SCASML_ERR_ARG, "plan_stage_list: plan.sites is inconsistent with its terms");

@@ -1,27 +1,16 @@
 """``MLP`` with the reference's call surface (solvers/MLP.py:5-288), running on libscasml_hip."""
 from .. import tables
-from ._picard import PicardEngine, deliver
+from ._picard import PicardSolver, deliver
 
 
-class MLP:
+class MLP(PicardSolver):
     '''Multilevel Picard Iteration for high dimensional semilinear PDE (solvers/MLP.py:5-25)'''
     _variant = "quad"
 
     def __init__(self, equation, seed=0, compat_crn=False, compat_f16=False, compat_rng=None, reference_mode=False):
         """reference_mode=True: what the reference's solver object computes -- its random stream under its key schedule
         (compat_rng="jax") and its solver-level float16 casts (compat_f16) -- in one switch."""
-        self.equation = equation
-        self.sigma = equation.sigma
-        self.mu = equation.mu
-        equation.geometry()
-        self.T = equation.T
-        self.t0 = equation.t0
-        self.n_input = equation.n_input
-        self.n_output = equation.n_output
-        self.evaluation_counter = 0
-        self.key = seed                      # Philox seed; replaces random.PRNGKey(0) (:25)
-        self._engine = PicardEngine(equation, self._variant, gp=None, seed=seed, compat_crn=compat_crn, compat_f16=compat_f16, compat_rng=compat_rng,
-                                    reference_mode=reference_mode)
+        super().__init__(equation, None, seed, compat_crn=compat_crn, compat_f16=compat_f16, compat_rng=compat_rng, reference_mode=reference_mode)
 
     def f(self, x_t, u, z):
         return self.equation.f(x_t, u, z)                         # :27-41
@@ -45,9 +34,8 @@ class MLP:
         error of u (of the unclipped root sum; the Picard truncation bias is not in it): scasml_picard_tree_stderr in include/scasml_hip.h.
         ValueError where a term of the root call has one sample (rho <= 2).'''
         self.Mf, self.Mg, self.Q, self.c, self.w = self.approx_parameters(rho)
-        uz, _, was_numpy, *se = self._engine.solve(int(n), int(rho), x_t, stderr=bool(return_stderr))
-        self.evaluation_counter += self._engine.evaluation_increment(int(n), int(rho))
-        return (deliver(uz, was_numpy), deliver(se[0][:, None], was_numpy)) if return_stderr else deliver(uz, was_numpy)
+        uz, _, was_numpy, se = self._solve(n, rho, x_t, return_stderr)
+        return deliver(uz, was_numpy, se)
 
     def u_solve(self, n, rho, x_t, return_stderr=False):
         if return_stderr:

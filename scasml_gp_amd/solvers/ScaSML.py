@@ -1,28 +1,17 @@
 """``ScaSML`` (solvers/ScaSML.py:5-304): multilevel Picard on the defect u - u_GP, on libscasml_hip."""
 from .. import tables
-from ._picard import PicardEngine, deliver
+from ._picard import PicardSolver, deliver
 
 
-class ScaSML:
+class ScaSML(PicardSolver):
     '''Multilevel Picard Iteration calibrated GP for high dimensional semilinear PDE'''
     _variant = "quad"
 
     def __init__(self, equation, GP, seed=0, compat_crn=False, compat_f16=False, compat_rng=None, reference_mode=False):
         """reference_mode=True: the reference's random stream under its key schedule (compat_rng="jax") and its solver-level float16
         casts (compat_f16) in one switch; with the default GP (compat="reference") that is the reference's ScaSML."""
-        self.equation = equation
-        self.sigma = equation.sigma
-        self.mu = equation.mu
-        equation.geometry()
-        self.T = equation.T
-        self.t0 = equation.t0
-        self.n_input = equation.n_input
-        self.n_output = equation.n_output
         self.GP = GP
-        self.evaluation_counter = 0
-        self.key = seed
-        self._engine = PicardEngine(equation, self._variant, gp=GP, seed=seed, compat_crn=compat_crn, compat_f16=compat_f16, compat_rng=compat_rng,
-                                    reference_mode=reference_mode)
+        super().__init__(equation, GP, seed, compat_crn=compat_crn, compat_f16=compat_f16, compat_rng=compat_rng, reference_mode=reference_mode)
 
     def __setattr__(self, name, value):
         object.__setattr__(self, name, value)
@@ -50,18 +39,12 @@ class ScaSML:
     def approx_parameters(self, rhomax):
         return tables.approx_parameters(int(rhomax), float(self.T))
 
-    def _solve(self, n, par, x_t, stderr=False):
-        """-> (uz, u_hat, was_numpy, se): se the (batch, 1) standard error of u_breve, or None."""
-        uz, uhat, was_numpy, *se = self._engine.solve(int(n), int(par), x_t, stderr=bool(stderr))
-        self.evaluation_counter += self._engine.evaluation_increment(int(n), int(par))
-        return uz, uhat, was_numpy, (se[0][:, None] if stderr else None)
-
     def uz_solve(self, n, rho, x_t, return_stderr=False):
         '''solvers/ScaSML.py:149-284.  return_stderr=True: (uz, se), se the (batch, 1) float32 Monte-Carlo standard error of u_breve
         (scasml_picard_tree_stderr in include/scasml_hip.h); ValueError where a term of the root call has one sample (rho <= 2).'''
         self.Mf, self.Mg, self.Q, self.c, self.w = self.approx_parameters(rho)       # :161
         uz, _, was_numpy, se = self._solve(n, rho, x_t, return_stderr)
-        return (deliver(uz, was_numpy), deliver(se, was_numpy)) if return_stderr else deliver(uz, was_numpy)
+        return deliver(uz, was_numpy, se)
 
     def u_solve(self, n, rho, x_t, return_stderr=False):
         '''u_hat + u_breve, solvers/ScaSML.py:286-304.  return_stderr=True: (u, se) with se the (batch, 1) float32 standard error of the
@@ -70,8 +53,7 @@ class ScaSML:
         bias are not in it, and the clip of u_breve is not modelled.'''
         self.Mf, self.Mg, self.Q, self.c, self.w = self.approx_parameters(rho)
         uz, uhat, was_numpy, se = self._solve(n, rho, x_t, return_stderr)
-        u = deliver(self._sum16(uz[:, 0:1] + uhat[:, None]), was_numpy)
-        return (u, deliver(se, was_numpy)) if return_stderr else u
+        return deliver(self._sum16(uz[:, 0:1] + uhat[:, None]), was_numpy, se)
 
     def _sum16(self, total):
         """compat_f16: u_breve + u_hat is a float16 sum in the reference (:300-304: u_breve float16 by :284 -- in the full-history solver by

@@ -232,12 +232,9 @@ class PicardEngine:
             return out, None, was_numpy
         if self.gp is None:
             if stderr:
-                _lib.check(self._timed("picard_mlp_stderr", lambda: lib.scasml_picard_tree_stderr(
-                    C.byref(prob), C.byref(plan), _lib.MODE_MLP, _lib.ptr(x), B, 0, rng, None, None, _lib.ptr(out), None, _lib.ptr(se), s)),
-                    "picard_tree_stderr")
+                self._tree("picard_mlp_stderr", "picard_tree_stderr", prob, plan, _lib.MODE_MLP, x, B, 0, rng, s, out=out, se=se)
                 return out, None, was_numpy, se
-            _lib.check(self._timed("picard_mlp", lambda: lib.scasml_picard_tree(
-                C.byref(prob), C.byref(plan), _lib.MODE_MLP, _lib.ptr(x), B, 0, rng, None, None, _lib.ptr(out), None, s)), "picard_tree")
+            self._tree("picard_mlp", "picard_tree", prob, plan, _lib.MODE_MLP, x, B, 0, rng, s, out=out)
             self._jax_commit(jax_next, stream_id)
             return out, None, was_numpy
         uhat = torch.empty((B,), dtype=torch.float32, device="cuda")
@@ -260,19 +257,14 @@ class PicardEngine:
             xc = x[b0:b0 + nb]
             if n > 0:
                 ob, ub = out[b0:b0 + nb], uhat[b0:b0 + nb]
-                _lib.check(self._timed("picard_generate", lambda: lib.scasml_picard_tree(
-                    C.byref(prob), C.byref(plan), _lib.MODE_GENERATE, _lib.ptr(xc), nb, stride, rng_c,
-                    _lib.ptr(pts), None, None, None, s)), "picard_tree(generate)")
+                self._tree("picard_generate", "picard_tree(generate)", prob, plan, _lib.MODE_GENERATE, xc, nb, stride, rng_c, s, pts=pts)
                 self._timed("gp_eval", lambda: self.gp._eval_rows(pts, stride * ppr, stride, kinds, vals, x_bound=x_bound, order=order))
                 if stderr:
-                    sb = se[b0:b0 + nb]
-                    _lib.check(self._timed("picard_accumulate_stderr", lambda: lib.scasml_picard_tree_stderr(
-                        C.byref(prob), C.byref(plan), _lib.MODE_ACCUMULATE, _lib.ptr(xc), nb, stride, rng_c,
-                        _lib.ptr(pts), _lib.ptr(vals), _lib.ptr(ob), _lib.ptr(ub), _lib.ptr(sb), s)), "picard_tree_stderr(accumulate)")
+                    self._tree("picard_accumulate_stderr", "picard_tree_stderr(accumulate)", prob, plan, _lib.MODE_ACCUMULATE, xc, nb, stride, rng_c, s,
+                               pts=pts, vals=vals, out=ob, uhat=ub, se=se[b0:b0 + nb])
                 else:
-                    _lib.check(self._timed("picard_accumulate", lambda: lib.scasml_picard_tree(
-                        C.byref(prob), C.byref(plan), _lib.MODE_ACCUMULATE, _lib.ptr(xc), nb, stride, rng_c,
-                        _lib.ptr(pts), _lib.ptr(vals), _lib.ptr(ob), _lib.ptr(ub), s)), "picard_tree(accumulate)")
+                    self._tree("picard_accumulate", "picard_tree(accumulate)", prob, plan, _lib.MODE_ACCUMULATE, xc, nb, stride, rng_c, s,
+                               pts=pts, vals=vals, out=ob, uhat=ub)
             else:                          # n == 0: zeros (ScaSML.py:217-219); u_hat still needed by u_solve
                 out[b0:b0 + nb].zero_()
                 uhat[b0:b0 + nb] = self.gp._predict_device(xc)[:, 0]
@@ -280,6 +272,16 @@ class PicardEngine:
                     se[b0:b0 + nb].zero_()
         self._jax_commit(jax_next, stream_id)
         return (out, uhat, was_numpy, se) if stderr else (out, uhat, was_numpy)
+
+    def _tree(self, timer, what, prob, plan, mode, x, nb, stride, rng, s, pts=None, vals=None, out=None, uhat=None, se=None):
+        """One Picard-tree launch over ``nb`` roots under its timer name; ``se`` given: the kernels that also estimate the standard error
+        of u (scasml_picard_tree_stderr).  ``what`` names the call in the error a refusal raises."""
+        lib = _lib.load()
+        args = (C.byref(prob), C.byref(plan), mode, _lib.ptr(x), nb, stride, rng, _lib.ptr(pts), _lib.ptr(vals), _lib.ptr(out), _lib.ptr(uhat))
+        if se is None:
+            _lib.check(self._timed(timer, lambda: lib.scasml_picard_tree(*args, s)), what)
+        else:
+            _lib.check(self._timed(timer, lambda: lib.scasml_picard_tree_stderr(*args, _lib.ptr(se), s)), what)
 
     def stage_lists(self, n, par):
         """Device lists of a staged solve (scasml_plan_stage_list), uploaded once per plan: int32 (base, origin) pairs per stage 1..n for
@@ -331,9 +333,7 @@ class PicardEngine:
             nb = min(chunk, B - b0)
             rng_c = _lib.Rng(rng.seed, rng.stream, rng.root0 + b0, 0, 1, 0, 0, None, None)   # root0 + b0: normals independent of the chunking
             xc = x[b0:b0 + nb]
-            _lib.check(self._timed("picard_staged_generate", lambda: lib.scasml_picard_tree(
-                C.byref(prob), C.byref(plan), _lib.MODE_GENERATE, _lib.ptr(xc), nb, chunk, rng_c, _lib.ptr(pts), None, None, None, s)),
-                "picard_tree(generate)")
+            self._tree("picard_staged_generate", "picard_tree(generate)", prob, plan, _lib.MODE_GENERATE, xc, nb, chunk, rng_c, s, pts=pts)
             xg = self._timed("picard_staged_gather", lambda: P[term, :nb, :d + 1].reshape(-1, d + 1).contiguous())
             gv = self._callback("g", eq.g, (xg,), xg.shape[0])
 
@@ -482,5 +482,32 @@ def _scalar_of(equation, what):
     return float(a)
 
 
-def deliver(t, was_numpy):
-    return t.cpu().numpy() if was_numpy else t
+def deliver(t, was_numpy, se=None):
+    """The caller's kind of array back (NumPy in, NumPy out); with ``se``, the standard error of a return_stderr call: the pair (t, se)."""
+    out = t.cpu().numpy() if was_numpy else t
+    return out if se is None else (out, deliver(se, was_numpy))
+
+
+class PicardSolver:
+    """What the four solver classes share: the attributes of the reference's solver objects, the engine, and the counted solve."""
+    _variant = None                      # "quad" or "fh"
+
+    def __init__(self, equation, GP, seed, **engine_options):
+        self.equation = equation
+        self.sigma = equation.sigma
+        self.mu = equation.mu
+        equation.geometry()
+        self.T = equation.T
+        self.t0 = equation.t0
+        self.n_input = equation.n_input
+        self.n_output = equation.n_output
+        self.evaluation_counter = 0
+        self.key = seed                      # Philox seed; replaces random.PRNGKey(0) (MLP.py:25)
+        self._engine = PicardEngine(equation, self._variant, gp=GP, seed=seed, **engine_options)
+
+    def _solve(self, n, par, x_t, stderr=False):
+        """One engine solve, counted as the reference counts its evaluations -> (uz, u_hat or None, was_numpy, se): se the (batch, 1)
+        standard error of the solved u, or None."""
+        uz, uhat, was_numpy, *se = self._engine.solve(int(n), int(par), x_t, stderr=bool(stderr))
+        self.evaluation_counter += self._engine.evaluation_increment(int(n), int(par))
+        return uz, uhat, was_numpy, (se[0][:, None] if stderr else None)

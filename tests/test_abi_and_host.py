@@ -52,6 +52,165 @@ def test_argument_errors_are_codes_not_crashes(lib):
     assert lib.scasml_trsm_lower(C.c_void_p(8), 33, C.c_void_p(8), 1, 0, None) == -2
 
 
+def test_picard_entry_points_refuse_in_a_fixed_order(lib):
+    """Every refusal of scasml_picard_tree, scasml_picard_tree_stderr, scasml_picard_stage and scasml_plan_stage_list, failing alone, and the
+    inputs that fail two checks at once: the code and the message are those of the FIRST check in the entry point's own order (the tree
+    answers an empty batch before it looks at d; the stage looks at an empty batch last).  Dummy non-null pointers: every case returns
+    before anything is launched or touched."""
+    p8 = C.c_void_p(8)
+    MLP, GEN, ACC = _lib.MODE_MLP, _lib.MODE_GENERATE, _lib.MODE_ACCUMULATE
+    base = tables.build_plan("quad", 3, 3, 0.5, True)
+    assert base.mg[3] >= 2 and all(base.term[3][l].mc >= 2 for l in range(3))       # a plan the stderr entry accepts
+
+    def plan(**kw):                    # a copy of the base plan with some fields replaced; term=(np, l, field, value)
+        p = _lib.Plan.from_buffer_copy(base)
+        for k, v in kw.items():
+            if k == "term":
+                setattr(p.term[v[0]][v[1]], v[2], v[3])
+            elif k == "mg":
+                p.mg[p.n] = v
+            elif k == "sites":
+                p.sites[p.n] = v
+            else:
+                setattr(p, k, v)
+        return C.byref(p)
+
+    def prob(d=20, eq=0):
+        return C.byref(_lib.Problem(d, eq, 0.5, -0.1, 0.25, 1.0))
+
+    def rng(rank=0, world=1, flags=0, keys=None):
+        return _lib.Rng(0, 0, 0, rank, world, flags, 0, None, keys)
+
+    JAX = _lib.RNG_JAX_STREAM
+
+    def tree(pr=None, pl=None, mode=MLP, x=p8, B=4, stride=0, r=None, pts=None, vals=None, out=p8):
+        return lib.scasml_picard_tree(pr or prob(), pl or plan(), mode, x, B, stride, r or rng(), pts, vals, out, None, None)
+
+    def tree_se(pr=None, pl=None, mode=MLP, B=4, r=None, pts=None, vals=None, se=p8):
+        return lib.scasml_picard_tree_stderr(pr or prob(), pl or plan(), mode, p8, B, 0, r or rng(), pts, vals, p8, None, se, None)
+
+    def stage(pr=None, pl=None, S=3, ent=p8, ne=1, B=4, stride=0, r=None, pts=p8, vals=p8, uz=p8, out=p8):
+        return lib.scasml_picard_stage(pr or prob(), pl or plan(), S, ent, ne, B, stride, r or rng(), pts, vals, uz, out, None)
+
+    def lst(pl=None, kind=_lib.STAGE_SUBTREES, S=1, out=None, cap=0):
+        return lib.scasml_plan_stage_list(pl or plan(), kind, S, out, cap)
+
+    table = [
+        # ---- scasml_picard_tree, one check at a time, in its order
+        (lambda: lib.scasml_picard_tree(None, plan(), MLP, p8, 4, 0, rng(), None, None, p8, None, None), -1, "picard_tree: null argument"),
+        (lambda: lib.scasml_picard_tree(prob(), None, MLP, p8, 4, 0, rng(), None, None, p8, None, None), -1, "picard_tree: null argument"),
+        (lambda: tree(B=-1), -1, "picard_tree: negative batch"),
+        (lambda: tree(B=4, stride=3), -1, "picard_tree: site_stride 3 is smaller than the batch 4"),
+        (lambda: tree(B=0), 0, None),
+        (lambda: tree(x=None), -1, "picard_tree: x_t is null"),
+        (lambda: tree(pr=prob(d=300)), -2, "picard_tree: d=300 outside 1..252"),
+        (lambda: tree(pr=prob(d=0)), -2, "picard_tree: d=0 outside"),
+        (lambda: tree(pr=prob(eq=9)), -2, "picard_tree: unknown equation id 9"),
+        (lambda: tree(pr=prob(eq=2), mode=ACC, pts=p8, vals=p8), -2, "runs in SCASML_MODE_MLP on the Philox stream only"),
+        (lambda: tree(pr=prob(eq=2), mode=GEN, pts=p8), -2, "runs in SCASML_MODE_MLP on the Philox stream only"),
+        (lambda: tree(pr=prob(eq=2), r=rng(flags=JAX, keys=8)), -2, "runs in SCASML_MODE_MLP on the Philox stream only"),
+        (lambda: tree(pl=plan(variant=2)), -1, "picard_tree: variant 2"),
+        (lambda: tree(pl=plan(n=6)), -2, "picard_tree: level n=6 outside 0..5"),
+        (lambda: tree(pl=plan(n=-1)), -2, "picard_tree: level n=-1 outside 0..5"),
+        (lambda: tree(r=rng(world=0)), -1, "picard_tree: bad rank/world"),
+        (lambda: tree(r=rng(rank=2, world=2)), -1, "picard_tree: bad rank/world"),
+        (lambda: tree(mode=GEN), -1, "picard_tree: GENERATE needs points"),
+        (lambda: tree(mode=ACC, pts=p8), -1, "picard_tree: ACCUMULATE needs gp_vals"),
+        (lambda: tree(mode=ACC, vals=p8), -1, "picard_tree: ACCUMULATE needs gp_vals"),
+        (lambda: tree(out=None), -1, "picard_tree: out_uz is null"),
+        (lambda: tree(pl=plan(term=(2, 1, "q", 0))), -1, "picard_tree: bad term [2][1]"),
+        (lambda: tree(pl=plan(term=(3, 0, "q", _lib.MAX_Q + 1))), -1, "picard_tree: bad term [3][0]"),
+        (lambda: tree(pl=plan(term=(1, 0, "mc", 0))), -1, "picard_tree: bad term [1][0]"),
+        (lambda: tree(pl=plan(n=0), mode=GEN, pts=p8), 0, None),                                    # level 0, nothing to emit
+        (lambda: tree(pl=plan(n=0), mode=GEN, pts=p8, r=rng(flags=JAX)), 0, None),                  # ... on the reference stream, keys not yet asked for
+        (lambda: tree(r=rng(flags=JAX)), -1, "picard_tree: SCASML_RNG_JAX_STREAM needs scasml_rng.jax_keys"),
+        (lambda: tree(pr=prob(d=1), B=1 << 38), -2, "picard_tree: batch too large"),               # 16 roots per wave, 4 waves per block
+        (lambda: tree(pr=prob(d=1), B=1 << 37, mode=GEN, pts=p8), -2, "picard_tree: batch too large"),   # GENERATE: 4 lanes per root
+        (lambda: tree(mode=7), -1, "picard_tree: unknown mode 7"),
+        (lambda: tree(mode=7, r=rng(flags=JAX, keys=8)), -1, "picard_tree: unknown mode 7"),
+        (lambda: tree(mode=-1, pr=prob(eq=1), pl=plan(variant=1)), -1, "picard_tree: unknown mode -1"),
+        # ---- two checks at once: the first in the tree's order answers
+        (lambda: tree(B=0, pr=prob(d=300)), 0, None),
+        (lambda: tree(B=0, x=None), 0, None),
+        (lambda: tree(B=0, pl=plan(term=(2, 1, "q", 0)), mode=7), 0, None),
+        (lambda: tree(B=4, stride=3, pr=prob(d=300)), -1, "picard_tree: site_stride 3 is smaller than the batch 4"),
+        (lambda: tree(B=-1, stride=-2, x=None), -1, "picard_tree: negative batch"),
+        (lambda: tree(x=None, pr=prob(d=300)), -1, "picard_tree: x_t is null"),
+        (lambda: tree(pr=prob(d=300, eq=9)), -2, "picard_tree: d=300"),
+        (lambda: tree(pr=prob(eq=2), mode=7), -2, "runs in SCASML_MODE_MLP"),
+        (lambda: tree(pl=plan(term=(2, 1, "q", 0)), out=None), -1, "picard_tree: out_uz is null"),
+        (lambda: tree(pl=plan(term=(2, 1, "q", 0)), mode=7), -1, "picard_tree: bad term [2][1]"),
+        # ---- scasml_picard_tree_stderr: the tree's checks under the tree's prefix, then its own
+        (lambda: tree_se(B=-1), -1, "picard_tree: negative batch"),
+        (lambda: tree_se(B=0, se=None, mode=GEN), 0, None),
+        (lambda: tree_se(mode=GEN, pts=p8), -1, "picard_tree_stderr: mode 1 has no estimate"),
+        (lambda: tree_se(mode=7), -1, "picard_tree_stderr: mode 7 has no estimate"),
+        (lambda: tree_se(se=None), -1, "picard_tree_stderr: out_se is null"),
+        (lambda: tree_se(r=rng(rank=1, world=2)), -2, "picard_tree_stderr: world = 2"),
+        (lambda: tree_se(r=rng(flags=_lib.RNG_COMPAT_CRN)), -2, "picard_tree_stderr: rng.flags = 1"),
+        (lambda: tree_se(pl=plan(mg=1)), -2, "picard_tree_stderr: the terminal term of level 3 has 1 sample"),
+        (lambda: tree_se(pl=plan(term=(3, 1, "mc", 1))), -2, "picard_tree_stderr: term [3][1] has 1 sample path"),
+        (lambda: tree_se(pr=prob(eq=2), mode=ACC, pts=p8, vals=p8), -2, "runs in SCASML_MODE_MLP on the Philox stream only"),
+        (lambda: tree_se(mode=GEN), -1, "picard_tree: GENERATE needs points"),
+        (lambda: tree_se(mode=GEN, pts=p8, se=None), -1, "picard_tree_stderr: mode 1 has no estimate"),
+        (lambda: tree_se(pl=plan(term=(2, 1, "q", 0)), se=None), -1, "picard_tree: bad term [2][1]"),
+        # ---- scasml_picard_stage, one check at a time, in its order
+        (lambda: lib.scasml_picard_stage(None, plan(), 3, p8, 1, 4, 0, rng(), p8, p8, p8, p8, None), -1, "picard_stage: null argument"),
+        (lambda: lib.scasml_picard_stage(prob(), None, 3, p8, 1, 4, 0, rng(), p8, p8, p8, p8, None), -1, "picard_stage: null argument"),
+        (lambda: stage(B=-1), -1, "picard_stage: negative batch"),
+        (lambda: stage(B=4, stride=3), -1, "picard_stage: site_stride 3 is smaller than the batch 4"),
+        (lambda: stage(pr=prob(d=300)), -2, "picard_stage: d=300 outside 1..252"),
+        (lambda: stage(pl=plan(variant=-1)), -1, "picard_stage: variant -1"),
+        (lambda: stage(pl=plan(n=0)), -2, "picard_stage: level n=0 outside 1..5"),
+        (lambda: stage(pl=plan(n=6)), -2, "picard_stage: level n=6 outside 1..5"),
+        (lambda: stage(S=0), -1, "picard_stage: stage 0 outside 1..3"),
+        (lambda: stage(S=4), -1, "picard_stage: stage 4 outside 1..3"),
+        (lambda: stage(r=rng(flags=1)), -2, "picard_stage: rng.flags 0x1"),
+        (lambda: stage(r=rng(rank=1, world=2)), -2, "picard_stage: sample sharding (world 2)"),
+        (lambda: stage(ne=0), -1, "picard_stage: no subtree entries"),
+        (lambda: stage(ent=None), -1, "picard_stage: no subtree entries"),
+        (lambda: stage(pl=plan(term=(3, 2, "mc", 0))), -1, "picard_stage: bad term [3][2]"),
+        (lambda: stage(B=0), 0, None),
+        (lambda: stage(pts=None), -1, "picard_stage: points and values are required"),
+        (lambda: stage(vals=None), -1, "picard_stage: points and values are required"),
+        (lambda: stage(S=2, uz=None), -1, "picard_stage: stage 2 of 3 needs uz"),
+        (lambda: stage(S=3, out=None), -1, "picard_stage: stage 3 of 3 needs out_uz"),
+        (lambda: stage(pr=prob(d=1), stride=1 << 28), -2, "picard_stage: site_stride 268435456 too large for 32-bit row offsets"),
+        (lambda: stage(pr=prob(d=1), ne=1 << 34), -2, "picard_stage: batch too large"),
+        (lambda: stage(pr=prob(d=1), B=64, ne=1 << 32), -2, "picard_stage: batch too large"),       # 16 roots per wave: 4 groups per entry
+        # ---- two checks at once: the first in the stage's order answers
+        (lambda: stage(B=0, pr=prob(d=300)), -2, "picard_stage: d=300"),
+        (lambda: stage(B=0, pl=plan(term=(2, 1, "q", 0))), -1, "picard_stage: bad term [2][1]"),
+        (lambda: stage(B=0, ne=0), -1, "picard_stage: no subtree entries"),
+        (lambda: stage(B=0, pts=None, vals=None, uz=None, out=None), 0, None),
+        (lambda: stage(B=4, stride=3, pr=prob(d=300)), -1, "picard_stage: site_stride 3"),
+        (lambda: stage(pr=prob(d=300), pl=plan(variant=2)), -2, "picard_stage: d=300"),
+        (lambda: stage(S=4, pl=plan(term=(2, 1, "q", 0))), -1, "picard_stage: stage 4 outside"),
+        (lambda: stage(pts=None, out=None), -1, "picard_stage: points and values are required"),
+        # ---- scasml_plan_stage_list
+        (lambda: lib.scasml_plan_stage_list(None, 0, 1, None, 0), -1, "plan_stage_list: bad plan (n must be 1..5)"),
+        (lambda: lst(pl=plan(n=0)), -1, "plan_stage_list: bad plan"),
+        (lambda: lst(S=0), -1, "plan_stage_list: subtrees of stage 0 outside 1..3"),
+        (lambda: lst(kind=_lib.STAGE_TERMINALS, S=1), -1, "plan_stage_list: the terminal list takes stage 0, got 1"),
+        (lambda: lst(kind=_lib.STAGE_F_AFTER, S=3), -1, "plan_stage_list: f-list after stage 3 outside 0..2"),
+        (lambda: lst(kind=7), -1, "plan_stage_list: unknown kind 7"),
+        (lambda: lst(cap=-1), -1, "plan_stage_list: negative capacity"),
+        (lambda: lst(pl=plan(term=(2, 0, "q", 0))), -1, "plan_stage_list: bad term [2][0]"),
+        (lambda: lst(pl=plan(term=(3, 2, "mc", 0))), -1, "plan_stage_list: bad term [3][2]"),
+        (lambda: lst(pl=plan(term=(2, 0, "q", 0)), cap=-1), -1, "plan_stage_list: negative capacity"),
+        (lambda: lst(pl=plan(sites=base.sites[3] + 1)), -1, "plan_stage_list: plan.sites is inconsistent with its terms"),
+        (lambda: lst(S=3), 1, None),                                                                 # counting: the root call is the one level-3 subtree
+        (lambda: lst(S=2, out=p8, cap=0), -1, "plan_stage_list: "),                                  # too small a list: refused before it is written
+    ]
+    for i, (call, code, text) in enumerate(table):
+        rc = call()
+        msg = lib.scasml_last_error().decode()
+        assert rc == code, (i, rc, code, msg)
+        if text is not None:
+            assert text in msg, (i, text, msg)
+    assert "entries, capacity 0" in lib.scasml_last_error().decode()
+
+
 @pytest.mark.parametrize("variant,n,par", [("quad", 1, 1), ("quad", 2, 2), ("quad", 3, 3), ("quad", 4, 4), ("quad", 2, 4),
                                             ("fh", 2, 3), ("fh", 3, 3), ("fh", 4, 3), ("fh", 3, 2)])
 def test_schedule_matches_oracle_counts(variant, n, par):
