@@ -212,8 +212,50 @@ struct Walker {
     int64_t local;     // this root's index inside the call's batch: row of site s = s * B + local
     int unit;          // running unit index of the ROOT call (sample sharding)
 
+    // Sum over the G lanes of a root's group, the same value in every lane: the xor butterfly o = G / 2, .., 1, every lane adding the value of
+    // lane i ^ o (float addition commutes: both partners get the same bits).  Only how the partner's value arrives is chosen per step: a
+    // run-time loop of ds_bpermute was five dependent LDS round trips per sum at d = 100 (address arithmetic, the LDS queue, an lgkmcnt wait
+    // and an add each), along a chain of 666 sites that each wave walks serially.  Now o = 8, 4, 2, 1 are DPP operands of the add itself
+    // (row_ror:8; row_half_mirror then a reversed quad, together lane i ^ 4; two quad permutations), o = 16 is one ds_swizzle (still an LDS-queue
+    // instruction, but without an address register), and o = 32 (d > 124 only) stays a ds_bpermute.  G is wave-uniform (a kernel argument): a
+    // scalar switch enters the ladder at its step.  (v_permlane16_swap for o = 16 was measured through inline assembly, the builtin's second
+    // result being unusable with this compiler: ACCUMULATE 4.2 ms against 1.07, profiles/r09_picard_dim_sum_ab.txt.)
+    // EVERY lane of the wave must be active at a call: a DPP or swizzle read of an inactive lane is not the partner's value.  It is so today
+    // -- ownership tests are scalar, idle lanes shadow the last root instead of leaving, and uz's per-lane `readback` branch closes before
+    // g_terminal -- and a call inside a lane-dependent branch would break it.
+    template <int CTRL>
+    static __device__ __forceinline__ float dpp(float v) {
+        return __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), CTRL, 0xF, 0xF, false));
+    }
     __device__ __forceinline__ float group_sum(float v) const {
-        for (int o = a.G >> 1; o > 0; o >>= 1) v += __shfl_xor(v, o);
+        // The reference-stream kernels keep the loop of ds_bpermute (the same sum, the same bits): with the ladder their ACCUMULATE n = 3 kernel
+        // went from 111 to 146 VGPRs and the parity mode's pass from 1.40 to 1.64 ms (profiles/r09_picard_dim_sum_ab.txt)
+        if constexpr (JAX) {
+            for (int o = a.G >> 1; o > 0; o >>= 1) v += __shfl_xor(v, o);
+            return v;
+        }
+        // Where the o = 32 step stands changes nothing but the register allocation, and that in opposite ways: as the switch's first case the
+        // MLP-mode kernels of quadrature n = 2 hold one VGPR more than with the loop (82 for 81; with standard errors 94 for 93), in front of
+        // the switch ACCUMULATE with standard errors grows from 94 to 101.  Each mode gets the place that costs it nothing
+        // (tests/test_picard_registers.py; profiles/r09_picard_dim_sum_ab.txt, "Registers").
+        constexpr bool kWideFirst = MODE == SCASML_MODE_MLP;
+        if constexpr (kWideFirst) {
+            if (a.logG == 6) v += __shfl_xor(v, 32);
+        }
+        switch (a.logG) {
+            case 6:
+                if constexpr (!kWideFirst) v += __shfl_xor(v, 32);
+                [[fallthrough]];
+            case 5: v += __builtin_bit_cast(float, __builtin_amdgcn_ds_swizzle(__builtin_bit_cast(int, v), 0x401F));   // swizzle(SWAP,16)
+                [[fallthrough]];
+            case 4: v += dpp<0x128>(v);                          // row_ror:8
+                [[fallthrough]];
+            case 3: v += dpp<0x1B>(dpp<0x141>(v));               // row_half_mirror, quad_perm:[3,2,1,0]
+                [[fallthrough]];
+            default:                                             // G >= 4 (fill_common_args)
+                v += dpp<0x4E>(v);                               // quad_perm:[2,3,0,1]
+                v += dpp<0xB1>(v);                               // quad_perm:[1,0,3,2]
+        }
         return v;
     }
     __device__ __forceinline__ float dim_sum(float4 v) const {
@@ -416,13 +458,20 @@ struct Walker {
                 float4 zc;
                 const uint32_t jkid = jfirst + (uint32_t)k * (1u + nsplits<L>() + nsplits<L - 1>()) + 1u;   // the children's first sub-key
                 const uint64_t jkrow = jrow * (uint32_t)mc + (uint32_t)m;
-                if (mine) {
-                    uz<L, false>(X, tk, base + o, (a.crn && VAR == 0) ? c_plus : base + o, uc, zc, jkrow, jkid);
-                    if constexpr (MODE != SCASML_MODE_GENERATE) {
-                        const float y = f_eval(uc, zc, gp) * (wk * inv_mc);
-                        u += y;                                  // MLP.py:248
-                        if constexpr (SE && TOP) ym += y;
-                        z = fma4(y * dplus, wvec, z);            // MLP.py:249
+                // ACCUMULATE at l = 0: the "+" addend is f(u_hat + 0, sigma div u_hat + dim_sum(0)) - f(u_hat, sigma div u_hat) under the zero child
+                // uz<0>, an exact +0 whenever f(u_hat, .) is finite, and u + 0 = u, fma(0 dplus, W, z) = z for finite dplus and W: it is not emitted
+                // (380 of the headline tree's 666 sites; one dim_sum and two f each).  Only the sign of a zero u or z can differ.  Where f(u_hat, .)
+                // is not finite the addend was NaN and made the root NaN; it still becomes NaN, through the residual addend below, whose eps_PDE
+                // contains the same f(u_hat, .).  MLP mode keeps the addend: f(0, 0) = 0 holds for the registered equations, not by construction.
+                if constexpr (!(MODE == SCASML_MODE_ACCUMULATE && L == 0)) {
+                    if (mine) {
+                        uz<L, false>(X, tk, base + o, (a.crn && VAR == 0) ? c_plus : base + o, uc, zc, jkrow, jkid);
+                        if constexpr (MODE != SCASML_MODE_GENERATE) {
+                            const float y = f_eval(uc, zc, gp) * (wk * inv_mc);
+                            u += y;                              // MLP.py:248
+                            if constexpr (SE && TOP) ym += y;
+                            z = fma4(y * dplus, wvec, z);        // MLP.py:249
+                        }
                     }
                 }
                 o += s_l;
@@ -570,7 +619,9 @@ __global__ __launch_bounds__(256) void picard_tree_kernel(const TreeArgs a) {
     if constexpr (MODE == SCASML_MODE_GENERATE) {
         // GENERATE takes no sum over dims: lanes need not form power-of-two groups.  Flat (root, quad) mapping over the
         // kp / 4 float4 of a row, so no lane idles through the Philox and the normal transform work (at d = 100: 28 lanes per root
-        // instead of 32, 25 of them drawing normals)
+        // instead of 32, 25 of them drawing normals).  (Mapping the lanes to the 25 quads that hold a spatial dim, with the row's other
+        // float4 -- t, padding -- as a second store of the root's first lanes, saves the three idle draws but was measured much slower:
+        // 1.66 ms against 1.08, profiles/r09_picard_dim_sum_ab.txt.  A row is written whole by neighbouring lanes of one store.)
         const int64_t flat = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
         const int quads = a.kp >> 2;
         local = flat / quads;
