@@ -185,6 +185,36 @@ int scasml_picard_tree_stderr(const scasml_problem *prob_h, const scasml_plan *p
                               float *out_uz, float *out_uhat, float *out_se, void *stream);
 
 /*
+ * scasml_picard_tree plus the Monte-Carlo standard errors of every root's u AND of every component of its z = sigma grad u (the reference
+ * has no counterpart).  (u, z) and u_hat are bit for bit those of scasml_picard_tree with the same arguments, and column 0 of out_se_uz is
+ * bit for bit the out_se of scasml_picard_tree_stderr.  Additive within ABI 7.
+ *   mode      : SCASML_MODE_MLP or SCASML_MODE_ACCUMULATE.  GENERATE has no estimate (run scasml_picard_tree): SCASML_ERR_ARG.
+ *   out_se_uz : B x (1+d) floats, required: (se_u, se_z_1 .. se_z_d) per root, the layout of out_uz.
+ * Definition.  The root call at level n computes z = Z_g + sum_{l<n} Z_l, component by component (u: scasml_picard_tree_stderr above).
+ *   Z_g = sum_{m<mg} P_m zs: P_m = g_m nrm_m, the terminal sample's normals times g_m = g(X_T^m) [MLP], (g - u_hat)(X_T^m) [ACCUMULATE];
+ *         zs = 1 / (mg (tau + 1e-6)) for the quadrature variant and 1 / (mg tau) for the full history (tau = T - t);  N_g = mg = plan.mg[n].
+ *   Z_l = sum_{m<mc} Q_{l,m}: Q_{l,m} is everything sample path m of term plan.term[n][l] adds to z, summed over its q nodes: the "+"
+ *         addend y+ dplus wvec, for l > 0 the "-" addend -y- dminus wvec and, in ACCUMULATE at l = 0, the surrogate's residual addend
+ *         e dminus wvec (wvec: the path's Brownian increment W_k, or the node's normals for the full history); N_l = mc.
+ *   The summands of a term own their RNG sites exactly as those of u do: i.i.d. given the root, the terms independent of each other.
+ *   Var(z_i) ~= sum_j N_j / (N_j - 1) sum_m (Y_{j,m,i} - mean_{j,i})^2, accumulated per term and per component on the deviations from the
+ *   term's first summand (S1 = sum D, S2 = sum D^2, N / (N - 1) (S2 - S1^2 / N)); the terminal term accumulates P_m and multiplies its
+ *   closed variance by zs^2.  out_se_uz = sqrt(Var) in float32, one per component; Var <= 0 gives 0 and a NaN passes through.
+ *   What se_z covers.  It is the Monte-Carlo error of the UNCLIPPED root sum, while the returned z is clipped to +-prob.clip: where a
+ *   component sits on the clip, se_z tells the caller how little the clipped value means (quadrature MLP, d = 20, n = 2, rho = 3, clip 1: the
+ *   median se of u is 0.06, that of a z component 0.65, and at an ordinary point, t = 0.31, 34 % of the returned components sit on the clip).
+ *   Where the unclipped z_i is NaN or +-inf, se_z_i is not finite either: a NaN in the root's row of x_t; quadrature rules whose tabulated
+ *   nodes are not increasing; the full history at t = T, where zs = 1 / 0 (the quadrature variant's epsilon keeps its se_z finite there).
+ *   Not included: the Picard truncation bias, the clips of the inner calls and, in ACCUMULATE, the surrogate's own error -- there se_z is that
+ *   of the correction z_breve.  Covariances between the components of z are not estimated.
+ * Refusals: those of scasml_picard_tree_stderr, with the same codes (a null out_se_uz or GENERATE: SCASML_ERR_ARG; rng.world != 1, rng.flags != 0,
+ * a term of one sample: SCASML_ERR_UNSUPPORTED).  plan.n == 0: out_uz and out_se_uz are zeros.  B == 0 does nothing.
+ */
+int scasml_picard_tree_stderr_uz(const scasml_problem *prob_h, const scasml_plan *plan_h, int mode, const float *x_t, int64_t B,
+                                 int64_t site_stride, scasml_rng rng, float *points, const float *gp_vals,
+                                 float *out_uz, float *out_uhat, float *out_se_uz, void *stream);
+
+/*
  * Staged Picard tree, for equations whose f and g are not in the registry (the driver evaluates them as batched torch
  * functions between launches; solvers/_picard.py).  A level-n solve runs SCASML_MODE_GENERATE of scasml_picard_tree once
  * (its points do not depend on the equation), then stages S = 1 .. n, each computing the (u, z) of every level-S subtree

@@ -51,7 +51,7 @@ __global__ void debug_jax_normals_kernel(uint32_t k0, uint32_t k1, uint64_t inde
 }
 
 int picard_tree_run(const scasml_problem *prob, const scasml_plan *plan, int mode, const float *x_t, int64_t B, int64_t site_stride, scasml_rng rng,
-                    float *points, const float *gp_vals, float *out_uz, float *out_uhat, float *out_se, bool want_se, void *stream) {
+                    float *points, const float *gp_vals, float *out_uz, float *out_uhat, float *out_se, SeWanted want_se, void *stream) {
     if (const int rc = check_batch("picard_tree", prob, plan, B, site_stride)) return rc;
     if (B == 0) return 0;
     if (!x_t) return fail(SCASML_ERR_ARG, "picard_tree: x_t is null");
@@ -70,10 +70,10 @@ int picard_tree_run(const scasml_problem *prob, const scasml_plan *plan, int mod
     if (mode != SCASML_MODE_GENERATE && !out_uz) return fail(SCASML_ERR_ARG, "picard_tree: out_uz is null");
     int np, lp;
     if (first_bad_term(*plan, np, lp)) return fail(SCASML_ERR_ARG, "picard_tree: bad term [%d][%d]", np, lp);
-    if (want_se) {   // scasml_picard_tree_stderr: what has no estimate is refused, never answered with a partial number
+    if (want_se) {   // scasml_picard_tree_stderr and _stderr_uz: what has no estimate is refused, never answered with a partial number
         if (mode != SCASML_MODE_MLP && mode != SCASML_MODE_ACCUMULATE)
             return fail(SCASML_ERR_ARG, "picard_tree_stderr: mode %d has no estimate (SCASML_MODE_MLP or SCASML_MODE_ACCUMULATE)", mode);
-        if (!out_se) return fail(SCASML_ERR_ARG, "picard_tree_stderr: out_se is null");
+        if (!out_se) return fail(SCASML_ERR_ARG, "picard_tree_stderr: %s is null", want_se == kSeUz ? "out_se_uz" : "out_se");
         if (rng.world != 1)
             return fail(SCASML_ERR_UNSUPPORTED, "picard_tree_stderr: world = %d: sample-sharded units split a path's addends across ranks, whose sums of squares do not add", rng.world);
         if (rng.flags != 0)
@@ -91,7 +91,8 @@ int picard_tree_run(const scasml_problem *prob, const scasml_plan *plan, int mod
             if (hipMemsetAsync(out_uz, 0, sizeof(float) * B * (prob->d + 1), s) != hipSuccess)
                 return fail(SCASML_ERR_HIP, "picard_tree: memset failed");
         }
-        if (want_se && hipMemsetAsync(out_se, 0, sizeof(float) * B, s) != hipSuccess) return fail(SCASML_ERR_HIP, "picard_tree_stderr: memset failed");
+        if (want_se && hipMemsetAsync(out_se, 0, sizeof(float) * B * (want_se == kSeUz ? prob->d + 1 : 1), s) != hipSuccess)
+            return fail(SCASML_ERR_HIP, "picard_tree_stderr: memset failed");
         return 0;
     }
     TreeArgs a;
@@ -115,6 +116,7 @@ int picard_tree_run(const scasml_problem *prob, const scasml_plan *plan, int mod
     const dim3 grid((unsigned)blocks);
     // the ladder (picard_tree.hpp) of the unit that holds the kernels: standard errors and the reference's stream have two units each
     const int v = plan->variant, eq = prob->eq_id, n = plan->n;
+    if (want_se == kSeUz) return n > 3 ? launch_tree_stderr_uz_deep(a, v, mode, eq, n, grid, s) : launch_tree_stderr_uz(a, v, mode, eq, n, grid, s);
     if (want_se) return n > 3 ? launch_tree_stderr_deep(a, v, mode, eq, n, grid, s) : launch_tree_stderr(a, v, mode, eq, n, grid, s);
     if (a.jk) return n > 3 ? launch_tree_jax_deep(a, v, mode, eq, n, grid, s) : launch_tree_jax(a, v, mode, eq, n, grid, s);
     return launch_tree<false, false, 1, SCASML_MAX_LEVEL>(a, v, mode, eq, n, grid, s);
@@ -127,7 +129,7 @@ using namespace scasml;
 extern "C" int scasml_picard_tree(const scasml_problem *prob, const scasml_plan *plan, int mode, const float *x_t,
                                   int64_t B, int64_t site_stride, scasml_rng rng, float *points, const float *gp_vals, float *out_uz,
                                   float *out_uhat, void *stream) {
-    return picard_tree_run(prob, plan, mode, x_t, B, site_stride, rng, points, gp_vals, out_uz, out_uhat, nullptr, false, stream);
+    return picard_tree_run(prob, plan, mode, x_t, B, site_stride, rng, points, gp_vals, out_uz, out_uhat, nullptr, kSeNone, stream);
 }
 
 extern "C" int scasml_debug_jax_normals(uint32_t key0, uint32_t key1, uint64_t index0, int64_t count, float *out, void *stream) {

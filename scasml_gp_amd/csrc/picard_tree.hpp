@@ -3,8 +3,10 @@
 //   picard_tree.hip                                        the Philox stream, levels 1..5; the entry points' validation (picard_tree_run)
 //   picard_tree_jax.hip / picard_tree_jax_deep.hip         the reference's own stream (SCASML_RNG_JAX_STREAM, compat_rng = "jax"), levels 1..3 / 4, 5
 //   picard_tree_stderr.hip / picard_tree_stderr_deep.hip   the kernels that also estimate the standard error of u, levels 1..3 / 4, 5
+//   picard_tree_stderr_uz.hip / picard_tree_stderr_uz_deep.hip   the kernels that estimate the standard errors of u and of every z_i
+//                                                          (picard_se_uz_kernel: the same walker under its SEZ flag), levels 1..3 / 4, 5
 //   picard_staged.hip                                      the staged walk (its own kernel; shares the lane helpers and the args filler below)
-// Each of the first five holds ONE call of launch_tree, whose <JAX, SE, N_LO, N_HI> decide what that unit compiles -- split so that the build
+// Each of the first seven holds ONE call of launch_tree, whose <JAX, SE, N_LO, N_HI, SEZ> decide what that unit compiles -- split so that the build
 // compiles the instantiations in parallel (the JAX-stream kernels inline one Threefry + erf_inv per normal at every site of the unrolled tree).
 #pragma once
 #include <string.h>
@@ -32,7 +34,8 @@ struct TreeArgs {
     const uint32_t *jk;   // SCASML_RNG_JAX_STREAM: key words [terminal k0 k1 | path sub-key 0 k0 k1 | sub-key 1 ...] (scasml_rng.jax_keys)
     int32_t d, G, logG, kp;
     float T, mu, sigma, clip;
-    float *out_se;   // picard_tree_kernel<..., SE = true> only: B standard errors of the root call's u (scasml_picard_tree_stderr)
+    float *out_se;   // picard_tree_kernel<..., SE = true> only: B standard errors of the root call's u (scasml_picard_tree_stderr);
+                     // picard_se_uz_kernel: B rows of 1 + d, the standard errors of (u, z_1 .. z_d) (scasml_picard_tree_stderr_uz)
 };
 
 __device__ __forceinline__ float4 f4(float v) { return make_float4(v, v, v, v); }
@@ -197,11 +200,46 @@ struct SeState {
 };
 template <>
 struct SeState<false> {};
+// The same estimate for z (scasml_picard_tree_stderr_uz), component by component: a summand is the float4 of this lane's four dims of what a
+// sample adds to the root call's z, so every lane accumulates its own dims and again nothing is shuffled.  Padding dims are accumulated
+// like the others (they may come to hold 0 * inf) and never stored.
+template <bool ON>
+struct SeTerm4 {
+    float4 y0, s1, s2;
+    __device__ __forceinline__ void begin() { y0 = s1 = s2 = make_float4(0.0f, 0.0f, 0.0f, 0.0f); }
+    __device__ __forceinline__ void add(float4 y, bool first) {
+        if (first) {
+            y0 = y;
+        } else {
+            const float4 dv = make_float4(y.x - y0.x, y.y - y0.y, y.z - y0.z, y.w - y0.w);
+            s1 = make_float4(s1.x + dv.x, s1.y + dv.y, s1.z + dv.z, s1.w + dv.w);
+            s2 = make_float4(fmaf(dv.x, dv.x, s2.x), fmaf(dv.y, dv.y, s2.y), fmaf(dv.z, dv.z, s2.z), fmaf(dv.w, dv.w, s2.w));
+        }
+    }
+    // N >= 2, as for SeTerm; scale: what the closed variance of the accumulated summands is multiplied by
+    __device__ __forceinline__ void close_into(float4 &var, int N, float scale) const {
+        const float fn = (float)N, c = fn / (fn - 1.0f);
+        var.x = fmaf(c * fmaf(-s1.x / fn, s1.x, s2.x), scale, var.x);
+        var.y = fmaf(c * fmaf(-s1.y / fn, s1.y, s2.y), scale, var.y);
+        var.z = fmaf(c * fmaf(-s1.z / fn, s1.z, s2.z), scale, var.z);
+        var.w = fmaf(c * fmaf(-s1.w / fn, s1.w, s2.w), scale, var.w);
+    }
+};
+template <>
+struct SeTerm4<false> {};
+template <bool ON>
+struct SezState {
+    float4 var;
+};
+template <>
+struct SezState<false> {};
 
-template <int VAR, int MODE, int EQ, bool JAX = false, bool SE = false>
+template <int VAR, int MODE, int EQ, bool JAX = false, bool SE = false, bool SEZ = false>
 struct Walker {
+    static_assert(!SEZ || SE, "the standard errors of z come with that of u");
     const TreeArgs &a;
     SeState<SE> se;    // SE: the variance estimate of the root call's u, summed over its terms (TOP frames only)
+    SezState<SEZ> sez; // SEZ: those of this lane's four dims of the root call's z
     float4 mask;       // 1 on this lane's live spatial dims, 0 on padding
     float4 tmask;      // 1 on the component that holds t in a stored row (column d)
     uint32_t row_off4; // (local * kp + 4 * gl) / 4: this lane's float4 inside a site's block of B rows
@@ -355,9 +393,12 @@ struct Walker {
         const float inv_mc = rcp_fast((float)mc);
         SeTerm<SE && TOP> st;
         if constexpr (SE && TOP) st.begin();
+        SeTerm4<SEZ && TOP> zt;
+        if constexpr (SEZ && TOP) zt.begin();
         for (int m = 0; m < mc; ++m) {
             float4 X = x, W = f4(0.0f);
             float ym = 0.0f;                                     // SE: what sample path m adds to u (unused otherwise)
+            float4 zm = f4(0.0f);                                // SEZ: what it adds to z
             // compat_crn: the children of every node k draw their terminal normals where the k = 0 children do
             // (MLP.py:167-168,178: one fixed key per uz_solve call, so calls of equal shape share their draws)
             const uint32_t c_plus = cbase + o + 1u, c_minus = c_plus + s_l;
@@ -471,6 +512,7 @@ struct Walker {
                             u += y;                              // MLP.py:248
                             if constexpr (SE && TOP) ym += y;
                             z = fma4(y * dplus, wvec, z);        // MLP.py:249
+                            if constexpr (SEZ && TOP) zm = fma4(y * dplus, wvec, zm);
                         }
                     }
                 }
@@ -483,6 +525,7 @@ struct Walker {
                             u -= y;                              // MLP.py:269
                             if constexpr (SE && TOP) ym -= y;
                             z = fma4(-y * dminus, wvec, z);      // MLP.py:271
+                            if constexpr (SEZ && TOP) zm = fma4(-y * dminus, wvec, zm);
                         }
                     }
                     o += s_lm;
@@ -491,11 +534,14 @@ struct Walker {
                     u += e;
                     if constexpr (SE && TOP) ym += e;
                     z = fma4(e * dminus, wvec, z);
+                    if constexpr (SEZ && TOP) zm = fma4(e * dminus, wvec, zm);
                 }
             }
             if constexpr (SE && TOP) st.add(ym, m == 0);
+            if constexpr (SEZ && TOP) zt.add(zm, m == 0);
         }
         if constexpr (SE && TOP) se.var += st.close(mc);
+        if constexpr (SEZ && TOP) zt.close_into(sez.var, mc, 1.0f);
         if constexpr (L + 1 < N) level<N, L + 1, TOP>(x, t, tau, base, cbase, o, u, z, jrow, jfirst + (uint32_t)q * (1u + nsplits<L>() + nsplits<L - 1>()));
     }
 
@@ -533,6 +579,8 @@ struct Walker {
             }
             SeTerm<SE && TOP> st;
             if constexpr (SE && TOP) st.begin();
+            SeTerm4<SEZ && TOP> zt;
+            if constexpr (SEZ && TOP) zt.begin();
             for (int m = 0; m < mg; ++m) {                       // MLP.py:175-202
                 const uint32_t site = base + (uint32_t)m;
                 float4 nrm, XT, gpv = f4(0.0f);
@@ -578,12 +626,15 @@ struct Walker {
                     su += g;
                     if constexpr (SE && TOP) st.add(g, m == 0);
                     sz = fma4(g, nrm, sz);
+                    if constexpr (SEZ && TOP) zt.add(f4_scale(nrm, g), m == 0);   // P_m = g nrm: what the line above adds
                 }
             }
             const float inv_mg = rcp_fast((float)mg);
             if constexpr (SE && TOP) se.var += st.close(mg) * (inv_mg * inv_mg);   // the summands are g / mg
             float u = su * inv_mg;
             const float zs = inv_mg * rcp_fast(VAR == 0 ? tau + 1e-6f : tau);   // MLP.py:201 / MLP_full_history.py:122
+            // the summands are P_m zs: at the full history's T - t = 0 the variance is that of inf P_m, inf or NaN and never a finite number
+            if constexpr (SEZ && TOP) zt.close_into(sez.var, mg, zs * zs);
             // padding dims carry sz = 0: at T - t = 0 the full-history scale is 1/0 (MLP_full_history.py:122 has no epsilon) and
             // 0 * inf would put a NaN into the padding that dim_sum's 0 * NaN then spreads to the whole root
             float4 z = make_float4(mask.x != 0.0f ? sz.x * zs : 0.0f, mask.y != 0.0f ? sz.y * zs : 0.0f,
@@ -677,8 +728,68 @@ __global__ __launch_bounds__(256) void picard_tree_kernel(const TreeArgs a) {
     }
 }
 
+// The standard errors of u and of every z_i (scasml_picard_tree_stderr_uz): the same walk under Walker's SEZ flag, a.out_se holding rows of
+// 1 + d.  A kernel template of its own, so that the names and argument lists of picard_tree_kernel's instances stay what they are; MLP and
+// ACCUMULATE on the Philox stream only, so the root set-up below is picard_tree_kernel's without its GENERATE and reference-stream branches.
+// (It is repeated here and not shared through an inlined function taking the arguments by reference: with one, five existing instances
+// changed their register counts -- <0,2,2,0> 89 -> 88 VGPRs, <0,2,5,0> 279 -> 280, the SE instance <0,2,5,1> 258 VGPRs and 3576 B of
+// scratch -> 138 and none -- and the existing kernels are to compile to the code they had: profiles/picard_stderr_uz_regs.txt.)
+template <int VAR, int MODE, int N, int EQ>
+__global__ __launch_bounds__(256) void picard_se_uz_kernel(const TreeArgs a) {
+    static_assert(MODE == SCASML_MODE_MLP || MODE == SCASML_MODE_ACCUMULATE, "standard errors: MLP and ACCUMULATE on the Philox stream");
+    normal_table_to_lds();                   // every thread, before any return below
+    const int lane = threadIdx.x & 63;
+    const int wave = (blockIdx.x * (blockDim.x >> 6)) + (threadIdx.x >> 6);
+    const int rpw = 64 >> a.logG;
+    int64_t local = (int64_t)wave * rpw + (lane >> a.logG);
+    const bool valid = local < a.B;
+    if (!valid) local = a.B - 1;  // idle lanes shadow the last root; their stores are masked
+
+    Walker<VAR, MODE, EQ, false, true, true> w{a};
+    w.se.var = 0.0f;
+    w.sez.var = f4(0.0f);
+    w.gl = (uint32_t)(lane & (a.G - 1));
+    w.root = a.root0 + (uint32_t)local;
+    w.local = local;
+    w.unit = 0;
+    const int dim0 = 4 * (int)w.gl;
+    w.mask = live_mask(dim0, a.d);
+    w.tmask = make_float4(dim0 + 0 == a.d ? 1.0f : 0.0f, dim0 + 1 == a.d ? 1.0f : 0.0f,
+                          dim0 + 2 == a.d ? 1.0f : 0.0f, dim0 + 3 == a.d ? 1.0f : 0.0f);
+    w.row_lane = dim0 < a.kp;
+    w.row_off4 = (uint32_t)((local * a.kp + (dim0 < a.kp ? dim0 : 0)) >> 2);
+    w.gp_off = (uint32_t)local;
+    const float *row = a.x_t + local * (a.d + 1);
+    float4 x;
+    x.x = dim0 + 0 < a.d ? row[dim0 + 0] : 0.0f;
+    x.y = dim0 + 1 < a.d ? row[dim0 + 1] : 0.0f;
+    x.z = dim0 + 2 < a.d ? row[dim0 + 2] : 0.0f;
+    x.w = dim0 + 3 < a.d ? row[dim0 + 3] : 0.0f;
+    const float t = row[a.d];
+
+    float u;
+    float4 z;
+    w.template uz<N, true>(x, t, 0u, 0u, u, z, (uint64_t)a.root0 + (uint64_t)local, 0u);
+    if (valid) {
+        float *out = a.out_uz + local * (a.d + 1);
+        float *se = a.out_se + local * (a.d + 1);            // (se_u, se_z_1 .. se_z_d), the layout of the out_uz row
+        if (w.gl == 0) {
+            out[0] = u;
+            if constexpr (MODE == SCASML_MODE_ACCUMULATE) {
+                if (a.out_uhat) a.out_uhat[local] = w.gp_at((uint32_t)(a.ppr - 1)).x;
+            }
+            se[0] = w.se.var <= 0.0f ? 0.0f : sqrtf(w.se.var);   // as picard_tree_kernel: Var <= 0 gives 0, a NaN Var stays NaN
+        }
+        store_z(out, dim0, a.d, z);
+        const float4 v = w.sez.var;                          // this lane's live dims; padding dims (which may hold 0 * inf) are not stored
+        store_z(se, dim0, a.d, make_float4(v.x <= 0.0f ? 0.0f : sqrtf(v.x), v.y <= 0.0f ? 0.0f : sqrtf(v.y),
+                                           v.z <= 0.0f ? 0.0f : sqrtf(v.z), v.w <= 0.0f ? 0.0f : sqrtf(v.w)));
+    }
+}
+
 // ---- the launch ladder ---------------------------------------------------------------------------
-// Which picard_tree_kernel<VAR, MODE, N, EQ, JAX, SE> exist, for either variant and every level of a unit's range -- the one statement of it:
+// Which picard_tree_kernel<VAR, MODE, N, EQ, JAX, SE> (SEZ: picard_se_uz_kernel<VAR, MODE, N, EQ>, which exist where the SE kernels do) exist,
+// for either variant and every level of a unit's range -- the one statement of it:
 //   GENERATE evaluates neither f nor g, so one instantiation (equation 0) serves every equation, and it has no sum to take an error of;
 //   an f of |z|^2 needs the surrogate's full gradient per site, so its equation runs surrogate-free (SCASML_MODE_MLP), and it is not one of
 //   the reference's, so never on the reference's stream;
@@ -692,8 +803,9 @@ constexpr bool tree_instance() {
 }
 
 // level n among N .. N_HI (a short compile-time recursion), then the launch
-template <int VAR, int MODE, int EQ, bool JAX, bool SE, int N, int N_HI>
+template <int VAR, int MODE, int EQ, bool JAX, bool SE, int N, int N_HI, bool SEZ>
 int launch_level(const TreeArgs &a, int n, dim3 grid, hipStream_t s) {
+    static_assert(!SEZ || SE, "the standard errors of z come with that of u");
     if constexpr (!tree_instance<MODE, EQ, JAX, SE>()) {
         return fail(SCASML_ERR_UNSUPPORTED, "picard_tree: no kernel for mode %d of equation id %d%s%s", MODE, EQ, JAX ? " on the reference's stream" : "",
                     SE ? " with standard errors" : "");
@@ -702,39 +814,41 @@ int launch_level(const TreeArgs &a, int n, dim3 grid, hipStream_t s) {
         return fail(SCASML_ERR_UNSUPPORTED, "%s level n=%d is not in this translation unit", SE ? "picard_tree_stderr:" : "picard_tree: SCASML_RNG_JAX_STREAM", n);
     } else {
         if (n == N) {
-            hipLaunchKernelGGL((picard_tree_kernel<VAR, MODE, N, EQ, JAX, SE>), grid, dim3(256), 0, s, a);
+            if constexpr (SEZ) hipLaunchKernelGGL((picard_se_uz_kernel<VAR, MODE, N, EQ>), grid, dim3(256), 0, s, a);
+            else hipLaunchKernelGGL((picard_tree_kernel<VAR, MODE, N, EQ, JAX, SE>), grid, dim3(256), 0, s, a);
             return check_launch(SE ? "picard_tree_stderr launch" : "picard_tree launch");
         }
-        return launch_level<VAR, MODE, EQ, JAX, SE, N + 1, N_HI>(a, n, grid, s);
+        return launch_level<VAR, MODE, EQ, JAX, SE, N + 1, N_HI, SEZ>(a, n, grid, s);
     }
 }
 
-template <int VAR, int MODE, bool JAX, bool SE, int N_LO, int N_HI>
+template <int VAR, int MODE, bool JAX, bool SE, int N_LO, int N_HI, bool SEZ>
 int launch_equation(const TreeArgs &a, int eq_id, int n, dim3 grid, hipStream_t s) {
     switch (MODE == SCASML_MODE_GENERATE ? SCASML_EQ_GRAD_DEPENDENT_NONLINEAR : eq_id) {   // the one redirection of GENERATE (tree_instance)
-        case SCASML_EQ_GRAD_DEPENDENT_NONLINEAR: return launch_level<VAR, MODE, SCASML_EQ_GRAD_DEPENDENT_NONLINEAR, JAX, SE, N_LO, N_HI>(a, n, grid, s);
-        case SCASML_EQ_CUBIC_REACTION_DIFFUSION: return launch_level<VAR, MODE, SCASML_EQ_CUBIC_REACTION_DIFFUSION, JAX, SE, N_LO, N_HI>(a, n, grid, s);
+        case SCASML_EQ_GRAD_DEPENDENT_NONLINEAR: return launch_level<VAR, MODE, SCASML_EQ_GRAD_DEPENDENT_NONLINEAR, JAX, SE, N_LO, N_HI, SEZ>(a, n, grid, s);
+        case SCASML_EQ_CUBIC_REACTION_DIFFUSION: return launch_level<VAR, MODE, SCASML_EQ_CUBIC_REACTION_DIFFUSION, JAX, SE, N_LO, N_HI, SEZ>(a, n, grid, s);
         case SCASML_EQ_QUADRATIC_GRADIENT_REACTION_DIFFUSION:
-            return launch_level<VAR, MODE, SCASML_EQ_QUADRATIC_GRADIENT_REACTION_DIFFUSION, JAX, SE, N_LO, N_HI>(a, n, grid, s);
+            return launch_level<VAR, MODE, SCASML_EQ_QUADRATIC_GRADIENT_REACTION_DIFFUSION, JAX, SE, N_LO, N_HI, SEZ>(a, n, grid, s);
     }
     return fail(SCASML_ERR_UNSUPPORTED, "picard_tree: unknown equation id %d", eq_id);
 }
 
-template <int VAR, bool JAX, bool SE, int N_LO, int N_HI>
+template <int VAR, bool JAX, bool SE, int N_LO, int N_HI, bool SEZ>
 int launch_mode(const TreeArgs &a, int mode, int eq_id, int n, dim3 grid, hipStream_t s) {
     switch (mode) {
-        case SCASML_MODE_MLP: return launch_equation<VAR, SCASML_MODE_MLP, JAX, SE, N_LO, N_HI>(a, eq_id, n, grid, s);
-        case SCASML_MODE_GENERATE: return launch_equation<VAR, SCASML_MODE_GENERATE, JAX, SE, N_LO, N_HI>(a, eq_id, n, grid, s);
-        case SCASML_MODE_ACCUMULATE: return launch_equation<VAR, SCASML_MODE_ACCUMULATE, JAX, SE, N_LO, N_HI>(a, eq_id, n, grid, s);
+        case SCASML_MODE_MLP: return launch_equation<VAR, SCASML_MODE_MLP, JAX, SE, N_LO, N_HI, SEZ>(a, eq_id, n, grid, s);
+        case SCASML_MODE_GENERATE: return launch_equation<VAR, SCASML_MODE_GENERATE, JAX, SE, N_LO, N_HI, SEZ>(a, eq_id, n, grid, s);
+        case SCASML_MODE_ACCUMULATE: return launch_equation<VAR, SCASML_MODE_ACCUMULATE, JAX, SE, N_LO, N_HI, SEZ>(a, eq_id, n, grid, s);
     }
     return fail(SCASML_ERR_ARG, "picard_tree: unknown mode %d", mode);
 }
 
-// A translation unit's kernels are those of the ONE launch_tree<JAX, SE, N_LO, N_HI> it instantiates: every variant, mode and equation of
+// A translation unit's kernels are those of the ONE launch_tree<JAX, SE, N_LO, N_HI, SEZ> it instantiates: every variant, mode and equation of
 // tree_instance at levels N_LO .. N_HI.  Refuses an unknown mode, then a level outside the unit's range; launches nothing it refuses.
-template <bool JAX, bool SE, int N_LO, int N_HI>
+template <bool JAX, bool SE, int N_LO, int N_HI, bool SEZ = false>
 int launch_tree(const TreeArgs &a, int variant, int mode, int eq_id, int n, dim3 grid, hipStream_t s) {
-    return variant == 0 ? launch_mode<0, JAX, SE, N_LO, N_HI>(a, mode, eq_id, n, grid, s) : launch_mode<1, JAX, SE, N_LO, N_HI>(a, mode, eq_id, n, grid, s);
+    return variant == 0 ? launch_mode<0, JAX, SE, N_LO, N_HI, SEZ>(a, mode, eq_id, n, grid, s)
+                        : launch_mode<1, JAX, SE, N_LO, N_HI, SEZ>(a, mode, eq_id, n, grid, s);
 }
 
 // the reference's own random stream (compat_rng = "jax"): picard_tree_jax.hip (n <= 3) and picard_tree_jax_deep.hip (n = 4, 5)
@@ -743,6 +857,9 @@ int launch_tree_jax_deep(const TreeArgs &a, int variant, int mode, int eq_id, in
 // the kernels that also estimate the standard error of u (SE = true): picard_tree_stderr.hip (n <= 3) and picard_tree_stderr_deep.hip (n = 4, 5)
 int launch_tree_stderr(const TreeArgs &a, int variant, int mode, int eq_id, int n, dim3 grid, hipStream_t s);
 int launch_tree_stderr_deep(const TreeArgs &a, int variant, int mode, int eq_id, int n, dim3 grid, hipStream_t s);
+// the kernels that estimate the standard errors of u and of every z_i (SE and SEZ): picard_tree_stderr_uz.hip (n <= 3) and picard_tree_stderr_uz_deep.hip (n = 4, 5)
+int launch_tree_stderr_uz(const TreeArgs &a, int variant, int mode, int eq_id, int n, dim3 grid, hipStream_t s);
+int launch_tree_stderr_uz_deep(const TreeArgs &a, int variant, int mode, int eq_id, int n, dim3 grid, hipStream_t s);
 // The fields TreeArgs and StageArgs (picard_staged.hip) have in common: the plan, the batch and its site-major row geometry, the Philox key
 // and the problem's constants.  Returns the roots a wavefront holds, 64 / G, which sizes either grid.
 template <class Args>
@@ -767,8 +884,10 @@ int fill_common_args(Args &a, const scasml_problem *prob, const scasml_plan *pla
     return 64 / a.G;
 }
 
-// scasml_picard_tree and scasml_picard_tree_stderr (out_se non-null selects the latter's kernels): one validation, one launch geometry
+// scasml_picard_tree, scasml_picard_tree_stderr and scasml_picard_tree_stderr_uz (want_se selects the kernels and says what out_se holds):
+// one validation, one launch geometry
+enum SeWanted { kSeNone = 0, kSeU = 1, kSeUz = 2 };   // no estimate; B standard errors of u; B rows of 1 + d, those of (u, z)
 int picard_tree_run(const scasml_problem *prob, const scasml_plan *plan, int mode, const float *x_t, int64_t B, int64_t site_stride, scasml_rng rng,
-                    float *points, const float *gp_vals, float *out_uz, float *out_uhat, float *out_se, bool want_se, void *stream);
+                    float *points, const float *gp_vals, float *out_uz, float *out_uhat, float *out_se, SeWanted want_se, void *stream);
 
 }  // namespace scasml

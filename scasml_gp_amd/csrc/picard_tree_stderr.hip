@@ -16,5 +16,5 @@ using namespace scasml;
 extern "C" int scasml_picard_tree_stderr(const scasml_problem *prob, const scasml_plan *plan, int mode, const float *x_t, int64_t B,
                                          int64_t site_stride, scasml_rng rng, float *points, const float *gp_vals, float *out_uz,
                                          float *out_uhat, float *out_se, void *stream) {
-    return picard_tree_run(prob, plan, mode, x_t, B, site_stride, rng, points, gp_vals, out_uz, out_uhat, out_se, true, stream);
+    return picard_tree_run(prob, plan, mode, x_t, B, site_stride, rng, points, gp_vals, out_uz, out_uhat, out_se, kSeU, stream);
 }

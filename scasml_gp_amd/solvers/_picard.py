@@ -171,9 +171,9 @@ class PicardEngine:
         return p
 
     def stderr_supported(self, n, par):
-        """(ok, reason): can ``solve(n, par, ..., stderr=True)`` estimate the standard error of u?  Host only, from the plan: a term of the
-        root call with ONE sample has no estimable variance (quadrature rho <= 2, full history M = 1) and such a plan is refused, never
-        answered with a partial number."""
+        """(ok, reason): can ``solve(n, par, ..., stderr=True)`` (or ``stderr="uz"``: the same rule) estimate the standard error of u?  Host
+        only, from the plan: a term of the root call with ONE sample has no estimable variance (quadrature rho <= 2, full history M = 1) and
+        such a plan is refused, never answered with a partial number."""
         plan = self.plan(n, par)
         if n > 0 and int(plan.mg[n]) < 2:
             return False, "the terminal term of level %d has %d sample: no estimable variance" % (n, int(plan.mg[n]))
@@ -185,6 +185,8 @@ class PicardEngine:
     def solve(self, n, par, x_t, root0=0, rank=0, world=1, stream_id=None, stderr=False):
         """-> (uz (B, 1+d), u_hat (B,) or None) as torch CUDA tensors, plus was_numpy; with ``stderr`` also, last, the (B,) float32 Monte-Carlo
         standard error of u (scasml_picard_tree_stderr in include/scasml_hip.h: the definition, what it covers and what it leaves out).
+        ``stderr="uz"``: last, instead, the (B, 1 + d) float32 standard errors of (u, z_1 .. z_d) (scasml_picard_tree_stderr_uz), column 0
+        bit for bit the (B,) result; every refusal of ``stderr=True`` holds for it.
         The call counter moves as in a plain solve, so calls with and without error bars can be mixed without moving any call's stream."""
         torch = _lib.require_gpu()
         lib = _lib.load()
@@ -193,6 +195,7 @@ class PicardEngine:
         if x.dim() != 2 or x.shape[1] != d + 1:
             raise ValueError("x_t must have shape (batch, %d), got %s" % (d + 1, tuple(x.shape)))
         B = x.shape[0]
+        se_uz = isinstance(stderr, str) and stderr == "uz"
         if self.callbacks and world > 1:
             raise NotImplementedError("equation %s has torch callbacks: a staged solve is not sample-sharded" % type(self.equation).__name__)
         if stderr:
@@ -225,14 +228,14 @@ class PicardEngine:
         if stream_id is None:
             self.calls += 1
         out = torch.empty((B, d + 1), dtype=torch.float32, device="cuda")
-        se = torch.empty((B,), dtype=torch.float32, device="cuda") if stderr else None
+        se = torch.empty((B, d + 1) if se_uz else (B,), dtype=torch.float32, device="cuda") if stderr else None
         s = _lib.stream_ptr()
         if self.callbacks:
             self._solve_staged(n, par, plan, prob, x, out, rng, s)
             return out, None, was_numpy
         if self.gp is None:
             if stderr:
-                self._tree("picard_mlp_stderr", "picard_tree_stderr", prob, plan, _lib.MODE_MLP, x, B, 0, rng, s, out=out, se=se)
+                self._tree("picard_mlp_stderr", "picard_tree_stderr", prob, plan, _lib.MODE_MLP, x, B, 0, rng, s, out=out, se=se, se_uz=se_uz)
                 return out, None, was_numpy, se
             self._tree("picard_mlp", "picard_tree", prob, plan, _lib.MODE_MLP, x, B, 0, rng, s, out=out)
             self._jax_commit(jax_next, stream_id)
@@ -261,7 +264,7 @@ class PicardEngine:
                 self._timed("gp_eval", lambda: self.gp._eval_rows(pts, stride * ppr, stride, kinds, vals, x_bound=x_bound, order=order))
                 if stderr:
                     self._tree("picard_accumulate_stderr", "picard_tree_stderr(accumulate)", prob, plan, _lib.MODE_ACCUMULATE, xc, nb, stride, rng_c, s,
-                               pts=pts, vals=vals, out=ob, uhat=ub, se=se[b0:b0 + nb])
+                               pts=pts, vals=vals, out=ob, uhat=ub, se=se[b0:b0 + nb], se_uz=se_uz)
                 else:
                     self._tree("picard_accumulate", "picard_tree(accumulate)", prob, plan, _lib.MODE_ACCUMULATE, xc, nb, stride, rng_c, s,
                                pts=pts, vals=vals, out=ob, uhat=ub)
@@ -273,13 +276,16 @@ class PicardEngine:
         self._jax_commit(jax_next, stream_id)
         return (out, uhat, was_numpy, se) if stderr else (out, uhat, was_numpy)
 
-    def _tree(self, timer, what, prob, plan, mode, x, nb, stride, rng, s, pts=None, vals=None, out=None, uhat=None, se=None):
+    def _tree(self, timer, what, prob, plan, mode, x, nb, stride, rng, s, pts=None, vals=None, out=None, uhat=None, se=None, se_uz=False):
         """One Picard-tree launch over ``nb`` roots under its timer name; ``se`` given: the kernels that also estimate the standard error
-        of u (scasml_picard_tree_stderr).  ``what`` names the call in the error a refusal raises."""
+        of u (scasml_picard_tree_stderr) or, with ``se_uz``, of u and every z_i into rows of 1 + d (scasml_picard_tree_stderr_uz).  ``what``
+        names the call in the error a refusal raises."""
         lib = _lib.load()
         args = (C.byref(prob), C.byref(plan), mode, _lib.ptr(x), nb, stride, rng, _lib.ptr(pts), _lib.ptr(vals), _lib.ptr(out), _lib.ptr(uhat))
         if se is None:
             _lib.check(self._timed(timer, lambda: lib.scasml_picard_tree(*args, s)), what)
+        elif se_uz:
+            _lib.check(self._timed(timer + "_uz", lambda: lib.scasml_picard_tree_stderr_uz(*args, _lib.ptr(se), s)), what)
         else:
             _lib.check(self._timed(timer, lambda: lib.scasml_picard_tree_stderr(*args, _lib.ptr(se), s)), what)
 
@@ -507,7 +513,8 @@ class PicardSolver:
 
     def _solve(self, n, par, x_t, stderr=False):
         """One engine solve, counted as the reference counts its evaluations -> (uz, u_hat or None, was_numpy, se): se the (batch, 1)
-        standard error of the solved u, or None."""
-        uz, uhat, was_numpy, *se = self._engine.solve(int(n), int(par), x_t, stderr=bool(stderr))
+        standard error of the solved u, with ``stderr="uz"`` the (batch, 1 + d) standard errors of (u, z), or None."""
+        se_uz = isinstance(stderr, str) and stderr == "uz"
+        uz, uhat, was_numpy, *se = self._engine.solve(int(n), int(par), x_t, stderr="uz" if se_uz else bool(stderr))
         self.evaluation_counter += self._engine.evaluation_increment(int(n), int(par))
-        return uz, uhat, was_numpy, (se[0][:, None] if stderr else None)
+        return uz, uhat, was_numpy, ((se[0] if se_uz else se[0][:, None]) if stderr else None)
