@@ -106,6 +106,7 @@ class PicardOracle:
         self.clip = eq.uncertainty if gp is not None else eq.norm_estimation
         self.sites_executed = 0
         self._rec = None                             # root_summands: the root call's summands, recorded beside the unchanged sums
+        self._rec_z = False                          # ... with what each sample adds to z in columns 1 .. d
 
     # reference call surface -------------------------------------------------
     def uz_solve(self, n, par, x_t, root0=0, rank=0, world=1, owner=None):
@@ -130,19 +131,22 @@ class PicardOracle:
                 self.jax_splits += self._jax_splits_in_call(n)
         return self._uz(n, x_t[:, :-1].copy(), x_t[:, -1].copy(), roots, 0, top=True, cbase=0, jx=jx)
 
-    def root_summands(self, n, par, x_t, root0=0):
+    def root_summands(self, n, par, x_t, root0=0, with_z=False):
         """The summands Y_{j,i} of the ROOT call (include/scasml_hip.h, scasml_picard_tree_stderr) from ONE walk of the tree:
         ``[Y_g, Y_0, ..., Y_{n-1}]``, float64 arrays of shape (N_j, B).  Y_g[m] = g(X_T^m) / mg ((g - u_hat) / mg with a surrogate);
         Y_l[m] is what sample path m of level l adds to u: over its q nodes the "+" addend, the "-" addend (l > 0) and the residual addend
-        (l = 0, with a surrogate), each with its 1 / mc.  Their total is the unclipped u.  Philox stream, one rank, no compat flags."""
+        (l = 0, with a surrogate), each with its 1 / mc.  Their total is the unclipped u.  Philox stream, one rank, no compat flags.
+
+        with_z=True (scasml_picard_tree_stderr_uz): arrays of shape (N_j, B, 1 + d); column 0 is the value above, columns 1 .. d what the same
+        sample adds to z -- G N / (mg (tau + eps)) for a terminal sample, the path's own running sum of its z addends for a level's."""
         if self.jax_stream or self.compat_crn or self.compat_f16:
             raise ValueError("root_summands: the Philox stream without compat flags only (CRN shares draws between summands)")
-        self._rec = []
+        self._rec, self._rec_z = [], bool(with_z)
         try:
             self.uz_solve(n, par, x_t, root0=root0)
             return [np.stack(Y) for Y in self._rec]
         finally:
-            self._rec = None
+            self._rec, self._rec_z = None, False
 
     def uz_call(self, level, par, x_t, root0=0, base=0):
         """(u, z) of ONE inner call of the recursion on the Philox stream: the level-``level`` call whose first RNG site is ``base``, started at
@@ -242,6 +246,10 @@ class PicardOracle:
         self._rec.append([])
         return self._rec[-1]
 
+    def _summand(self, y, zy):
+        """What root_summands records for one sample: its addition to u, and with_z its addition to z beside it."""
+        return np.concatenate([y[:, None], zy], axis=1) if self._rec_z else y
+
     def _uz(self, n, x, t, roots, base, top=False, cbase=None, jx=None):
         """base: first RNG site of this call's subtree.  cbase: where the call's TERMINAL draws
         come from -- equal to base except under compat_crn, where it is the base the call
@@ -273,7 +281,8 @@ class PicardOracle:
             sz += G[:, None] * N
             self.sites_executed += 1
             if rec is not None:
-                rec.append(G / mg)
+                with np.errstate(all="ignore"):
+                    rec.append(self._summand(G / mg, (G[:, None] * N) / (mg * (tau + eps))[:, None] if self._rec_z else None))
         with np.errstate(all="ignore"):
             return su / mg, sz / (mg * (tau + eps))[:, None]
 
@@ -310,8 +319,10 @@ class PicardOracle:
                 lp = l - 1                           # nodes of the previous level: q_prev x (1 + children's sub-keys)
                 jsplit += int(Q[rho - 1, n - lp - 1]) * (1 + self._jax_splits_in_call(lp) + (self._jax_splits_in_call(lp - 1) if lp else 0))
             rec = self._new_term(top)
+            rec_z = rec is not None and self._rec_z
             for m in range(mc):
                 ym = np.zeros(x.shape[0])            # root_summands: what this sample path adds to u
+                zm = np.zeros_like(x)                #                ... and to z
                 X = x.copy()
                 W = np.zeros_like(x)
                 o_k0 = o                             # offsets of this path's k=0 children (compat_crn)
@@ -350,6 +361,8 @@ class PicardOracle:
                         u = u + wloc[:, k] * y / mc                              # MLP.py:248
                         ym = ym + wloc[:, k] * y / mc
                         z = z + (wloc[:, k] * y)[:, None] * W / (mc * dplus[k])[:, None]   # MLP.py:249
+                        if rec_z:
+                            zm = zm + (wloc[:, k] * y)[:, None] * W / (mc * dplus[k])[:, None]
                     o += s_l
                     if l:
                         if owned_minus:
@@ -358,6 +371,8 @@ class PicardOracle:
                             u = u - wloc[:, k] * y / mc                          # MLP.py:269
                             ym = ym - wloc[:, k] * y / mc
                             z = z - (wloc[:, k] * y)[:, None] * W / (mc * dminus[k])[:, None]  # MLP.py:271
+                            if rec_z:
+                                zm = zm - (wloc[:, k] * y)[:, None] * W / (mc * dminus[k])[:, None]
                         o += s_lm
                     elif self.gp is not None:                                # ScaSML.py:274-280
                         P = np.concatenate([X, tk[:, None]], axis=1)
@@ -365,8 +380,10 @@ class PicardOracle:
                         u = u + wloc[:, k] * eps / mc
                         ym = ym + wloc[:, k] * eps / mc
                         z = z + (wloc[:, k] * eps)[:, None] * W / (mc * dminus[k])[:, None]
+                        if rec_z:
+                            zm = zm + (wloc[:, k] * eps)[:, None] * W / (mc * dminus[k])[:, None]
                 if rec is not None:
-                    rec.append(ym)
+                    rec.append(self._summand(ym, zm))
         return self._finish(u, z, top)
 
     def _uz_fh(self, n, x, t, roots, base, top, cbase, jx=None):
@@ -381,8 +398,10 @@ class PicardOracle:
             s_l = site_count("fh", l, M)
             s_lm = site_count("fh", l - 1, M) if l else 0
             rec = self._new_term(top)
+            rec_z = rec is not None and self._rec_z
             for m in range(mc):
                 ym = np.zeros(x.shape[0])                          # root_summands: what this sample adds to u
+                zm = np.zeros_like(x)                              #                ... and to z
                 owned = self._owned(top, unit)                     # the "+" addend of this (single-node) sample; "-" below for l > 0
                 unit += 1
                 owned_minus = False
@@ -416,6 +435,8 @@ class PicardOracle:
                     u = u + tau * y / mc                               # :157
                     ym = ym + tau * y / mc
                     z = z + (tau * y)[:, None] * wgt / mc
+                    if rec_z:
+                        zm = zm + (tau * y)[:, None] * wgt / mc
                 o += s_l
                 if l:
                     if owned_minus:
@@ -424,6 +445,8 @@ class PicardOracle:
                         u = u - tau * y / mc                           # :175
                         ym = ym - tau * y / mc
                         z = z - (tau * y)[:, None] * wgt / mc
+                        if rec_z:
+                            zm = zm - (tau * y)[:, None] * wgt / mc
                     o += s_lm
                 elif self.gp is not None:                          # ScaSML_full_history.py:189-195
                     P = np.concatenate([X, tk[:, None]], axis=1)
@@ -431,6 +454,8 @@ class PicardOracle:
                     u = u + tau * eps / mc
                     ym = ym + tau * eps / mc
                     z = z + (tau * eps)[:, None] * wgt / mc
+                    if rec_z:
+                        zm = zm + (tau * eps)[:, None] * wgt / mc
                 if rec is not None:
-                    rec.append(ym)
+                    rec.append(self._summand(ym, zm))
         return self._finish(u, z, top)
