@@ -235,6 +235,21 @@ int scasml_picard_stage(const scasml_problem *prob_h, const scasml_plan *plan_h,
                         int64_t n_entries, int64_t B, int64_t site_stride, scasml_rng rng, const float *points,
                         const float *values, float *uz, float *out_uz, void *stream);
 
+/*
+ * The root call of the staged tree, scasml_picard_stage at stage = plan.n, plus the Monte-Carlo standard errors of every root's u and of
+ * every component of its z -- the error bars of an equation with torch f and g.  out_uz is bit for bit that of scasml_picard_stage with the
+ * same arguments.  Additive within ABI 7.
+ *   out_se_uz : B x (1+d) floats, required: (se_u, se_z_1 .. se_z_d) per root, the layout of out_uz.
+ * Definition: that of scasml_picard_tree_stderr (u) and scasml_picard_tree_stderr_uz (z) in SCASML_MODE_MLP, with g_m and the nodes'
+ * f+ / f- read from `values`: what the estimate covers and what it leaves out is stated there and holds here word for word.
+ * Refusals: those of scasml_picard_stage, in its order; then stage != plan.n (only the root call has an estimate) and a null out_uz or
+ * out_se_uz: SCASML_ERR_ARG; plan.mg[n] < 2 or any plan.term[n][l].mc < 2 (one sample has no estimable variance): SCASML_ERR_UNSUPPORTED.
+ * B == 0 does nothing.
+ */
+int scasml_picard_stage_stderr(const scasml_problem *prob_h, const scasml_plan *plan_h, int32_t stage, const int32_t *entries, int64_t n_entries,
+                               int64_t B, int64_t site_stride, scasml_rng rng, const float *points, const float *values, float *out_uz,
+                               float *out_se_uz, void *stream);
+
 /* Clip all-reduced partial sums in place (world > 1): MLP.py:272-274 / ScaSML.py:281-284. */
 int scasml_clip(float *uz, int64_t count, float clip, void *stream);
 /* The same followed, when round16 != 0, by the root call's .astype(float16) (MLP.py:274, ScaSML.py:284, MLP_full_history.py:180 --

@@ -78,6 +78,8 @@ SIGNATURES = {
                                                C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "scasml_picard_stage": (C.c_int, [C.POINTER(Problem), C.POINTER(Plan), C.c_int32, C.c_void_p, C.c_int64, C.c_int64, C.c_int64, Rng,
                                       C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "scasml_picard_stage_stderr": (C.c_int, [C.POINTER(Problem), C.POINTER(Plan), C.c_int32, C.c_void_p, C.c_int64, C.c_int64, C.c_int64, Rng,
+                                             C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "scasml_clip": (C.c_int, [C.c_void_p, C.c_int64, C.c_float, C.c_void_p]),
     "scasml_clip_round16": (C.c_int, [C.c_void_p, C.c_int64, C.c_float, C.c_int32, C.c_void_p]),
     "scasml_debug_normals": (C.c_int, [Rng, C.c_uint32, C.c_int32, C.c_int64, C.c_void_p, C.c_void_p]),

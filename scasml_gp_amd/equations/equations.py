@@ -45,11 +45,16 @@ class Equation(object):
         is the clipping bound, ``geometry()`` sets ``T``.
       - Refused with ``NotImplementedError``: ScaSML / ScaSML_full_history and ``GP.GPsolver`` (the collocation operator needs
         ``f_parts``), ``reference_mode``, ``compat_rng="jax"``, ``compat_f16``, ``compat_crn`` and sample-sharded solves.
+      - ``staged_stderr = True``: ``u_solve`` / ``uz_solve(..., return_stderr=True | "uz")`` return the Monte-Carlo standard errors of
+        u and of every z_i, formed in the last stage of the staged tree (scasml_picard_stage_stderr in include/scasml_hip.h) under the
+        definition and the refusals of the fused solvers.  Left False, ``return_stderr`` raises ``NotImplementedError`` as it did
+        before the staged estimate existed.
 
     * Neither: the solvers refuse the equation with ``NotImplementedError``.
     """
     eq_id = None             # registry id of the fused kernels (csrc/equations.hpp)
     torch_callbacks = False  # eq_id None and this True: f and g are batched torch functions (staged Picard tree)
+    staged_stderr = False    # with torch_callbacks: return_stderr is answered from the staged tree's last stage
 
     def __init__(self, n_input, n_output=1):
         self.n_input = n_input

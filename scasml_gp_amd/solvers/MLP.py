@@ -38,7 +38,9 @@ class MLP(PicardSolver):
         UNCLIPPED root sum while the returned z is clipped: where a component sits on the clip, se_z says how little the clipped value
         means (d = 20, n = 2, rho = 3, clip 1: median se of u 0.06, of a z component 0.65; at an ordinary point, t = 0.31, 34 % of the
         returned components sit on the clip).  Where the unclipped z_i is NaN or infinite, se_z_i is not finite.  The truncation bias and
-        the inner calls' clips are not in it.'''
+        the inner calls' clips are not in it.
+        An equation with torch callbacks that sets staged_stderr = True (NotImplementedError without it) gets both estimates, under the same definition and refusals, from the last stage of the staged tree
+        (scasml_picard_stage_stderr).'''
         self.Mf, self.Mg, self.Q, self.c, self.w = self.approx_parameters(rho)
         uz, _, was_numpy, se = self._solve(n, rho, x_t, return_stderr)
         return deliver(uz, was_numpy, se)

@@ -186,7 +186,9 @@ class PicardEngine:
         """-> (uz (B, 1+d), u_hat (B,) or None) as torch CUDA tensors, plus was_numpy; with ``stderr`` also, last, the (B,) float32 Monte-Carlo
         standard error of u (scasml_picard_tree_stderr in include/scasml_hip.h: the definition, what it covers and what it leaves out).
         ``stderr="uz"``: last, instead, the (B, 1 + d) float32 standard errors of (u, z_1 .. z_d) (scasml_picard_tree_stderr_uz), column 0
-        bit for bit the (B,) result; every refusal of ``stderr=True`` holds for it.
+        bit for bit the (B,) result; every refusal of ``stderr=True`` holds for it.  An equation with torch callbacks that sets
+        ``staged_stderr = True`` gets the same estimate from the last stage of the staged tree (scasml_picard_stage_stderr); without the
+        attribute the solve raises NotImplementedError, as it always has for such equations.
         The call counter moves as in a plain solve, so calls with and without error bars can be mixed without moving any call's stream."""
         torch = _lib.require_gpu()
         lib = _lib.load()
@@ -199,8 +201,11 @@ class PicardEngine:
         if self.callbacks and world > 1:
             raise NotImplementedError("equation %s has torch callbacks: a staged solve is not sample-sharded" % type(self.equation).__name__)
         if stderr:
-            if self.callbacks:
-                raise NotImplementedError("equation %s has torch callbacks: the staged tree has no standard-error estimate" % type(self.equation).__name__)
+            # A callback equation asks for the staged estimate itself (Equation.staged_stderr); one that does not keeps the refusal such
+            # equations have met since the estimates exist, so that code written against it sees no change
+            if self.callbacks and not getattr(self.equation, "staged_stderr", False):
+                raise NotImplementedError("equation %s has torch callbacks: the staged tree estimates standard errors for equations that set "
+                                          "staged_stderr = True (scasml_picard_stage_stderr)" % type(self.equation).__name__)
             ok, why = self.stderr_supported(n, par)
             if not ok:
                 raise ValueError("no standard error for n = %d, %s = %d: %s" % (n, "rho" if self.variant == "quad" else "M", par, why))
@@ -228,11 +233,12 @@ class PicardEngine:
         if stream_id is None:
             self.calls += 1
         out = torch.empty((B, d + 1), dtype=torch.float32, device="cuda")
-        se = torch.empty((B, d + 1) if se_uz else (B,), dtype=torch.float32, device="cuda") if stderr else None
+        # (the staged tree's last stage always fills rows of 1 + d: stderr=True returns their column 0)
+        se = torch.empty((B, d + 1) if se_uz or self.callbacks else (B,), dtype=torch.float32, device="cuda") if stderr else None
         s = _lib.stream_ptr()
         if self.callbacks:
-            self._solve_staged(n, par, plan, prob, x, out, rng, s)
-            return out, None, was_numpy
+            self._solve_staged(n, par, plan, prob, x, out, rng, s, se=se)
+            return (out, None, was_numpy, se if se_uz else se[:, 0].contiguous()) if stderr else (out, None, was_numpy)
         if self.gp is None:
             if stderr:
                 self._tree("picard_mlp_stderr", "picard_tree_stderr", prob, plan, _lib.MODE_MLP, x, B, 0, rng, s, out=out, se=se, se_uz=se_uz)
@@ -315,16 +321,20 @@ class PicardEngine:
                              % (type(self.equation).__name__, name, rows, rows, args[0].device, got))
         return r.reshape(rows)
 
-    def _solve_staged(self, n, par, plan, prob, x, out, rng, s):
+    def _solve_staged(self, n, par, plan, prob, x, out, rng, s, se=None):
         """A solve for an equation with torch f and g, per root chunk: GENERATE every tree point; g on the terminal samples; then for
         S = 0 .. n-1 the stage-S kernel (S >= 1: the (u, z) of every level-S subtree) followed by f on every node whose child is now
-        known; the stage-n kernel writes ``out``.  Gathers and scatters are device indexing with the cached lists (stage_lists)."""
+        known; the stage-n kernel writes ``out``.  Gathers and scatters are device indexing with the cached lists (stage_lists).
+        ``se`` given, (B, 1 + d): the stage-n launch is scasml_picard_stage_stderr, which also writes the standard errors of (u, z) there
+        from the values the last callback left; nothing else of the solve changes."""
         torch = _lib.require_gpu()
         lib = _lib.load()
         eq = self.equation
         B, d = x.shape[0], x.shape[1] - 1
         if n == 0 or B == 0:                   # MLP.py:205-207: zeros, no callback
             out.zero_()
+            if se is not None:
+                se.zero_()
             return
         lists = self.stage_lists(n, par)
         ppr = int(lib.scasml_points_per_root(C.byref(plan)))
@@ -364,11 +374,16 @@ class PicardEngine:
                 def scatter():
                     V[node, :nb, slot] = fv.view(-1, nb)
                 self._timed("picard_staged_scatter", scatter)
-            self._stage(n, prob, plan, lists, nb, chunk, rng_c, pts, vals, uzb, out[b0:b0 + nb], s)
+            self._stage(n, prob, plan, lists, nb, chunk, rng_c, pts, vals, uzb, out[b0:b0 + nb], s, se=None if se is None else se[b0:b0 + nb])
 
-    def _stage(self, S, prob, plan, lists, nb, stride, rng, pts, vals, uzb, out, s):
+    def _stage(self, S, prob, plan, lists, nb, stride, rng, pts, vals, uzb, out, s, se=None):
         lib = _lib.load()
         ent = lists["subtrees"][S]
+        if se is not None:
+            _lib.check(self._timed("picard_staged_stage%d_stderr" % S, lambda: lib.scasml_picard_stage_stderr(
+                C.byref(prob), C.byref(plan), S, _lib.ptr(ent), ent.shape[0], nb, stride, rng, _lib.ptr(pts), _lib.ptr(vals),
+                _lib.ptr(out), _lib.ptr(se), s)), "picard_stage_stderr")
+            return
         _lib.check(self._timed("picard_staged_stage%d" % S, lambda: lib.scasml_picard_stage(
             C.byref(prob), C.byref(plan), S, _lib.ptr(ent), ent.shape[0], nb, stride, rng, _lib.ptr(pts), _lib.ptr(vals),
             _lib.ptr(uzb), _lib.ptr(out), s)), "picard_stage")
