@@ -229,18 +229,9 @@ def _worker_rccl(rank, world, port, case, q):
 
 
 def _run(world, case, timeout, worker=None):
-    import torch.multiprocessing as mp
-    ctx = mp.get_context("spawn")
-    q = ctx.Queue()
-    port = 29600 + (os.getpid() % 2000)
-    procs = [ctx.Process(target=worker or _worker, args=(r, world, port, case, q)) for r in range(world)]
-    for p in procs:
-        p.start()
-    res = sorted(q.get(timeout=timeout) for _ in procs)
-    for p in procs:
-        p.join(timeout=120)
-        assert p.exitcode == 0
-    return res
+    """One result per rank, sorted; the launcher (tests/_dist_ranks.py) leaves no rank alive, whatever happens."""
+    from _dist_ranks import run_ranks
+    return run_ranks(world, worker or _worker, (case,), timeout)
 
 
 def test_two_ranks_factor_M35k_to_the_single_gpu_factor():
