@@ -215,6 +215,53 @@ int scasml_picard_tree_stderr_uz(const scasml_problem *prob_h, const scasml_plan
                                  float *out_uz, float *out_uhat, float *out_se_uz, void *stream);
 
 /*
+ * Standard errors of a SAMPLE-SHARDED solve (rng.world > 1), which the two fused entries above refuse: instead of accumulating every summand
+ * Y_{j,m} of the definitions above into its term's variance, the walk STORES it -- under sample sharding the part of it this rank owns -- into a
+ * table; the ranks' tables add (one all-reduce, together with the partial (u, z)), and scasml_picard_summands_stderr closes the variance from
+ * the completed table.  The same routines of the reference as scasml_picard_tree (solvers/MLP.py:141-274, solvers/ScaSML.py:149-284,
+ * solvers/MLP_full_history.py:64-180, solvers/ScaSML_full_history.py:75-199); the reference has no counterpart for the error.  Additive within ABI 7.
+ *
+ * scasml_plan_root_summands (host): S = mg[n] + sum_{l<n} term[n][l].mc, the number of summands of the root call, and where every term's
+ *   lie: first_h[j], count_h[j] for j = 0 (the terminal samples) and j = 1 + l (the sample paths of level l), first_h[n + 1] = S; first_h needs
+ *   n + 2 entries, count_h n + 1; either may be NULL.  n = 0 gives 0 and writes nothing.  < 0 on error.
+ *
+ * scasml_picard_tree_summands: scasml_picard_tree plus the table.  out_uz and out_uhat are bit for bit those of scasml_picard_tree with the
+ *   same arguments -- at world > 1 the un-clipped partial sums.
+ *   mode  : SCASML_MODE_MLP or SCASML_MODE_ACCUMULATE.
+ *   ncol  : 1 -- the summands of u -- or 1 + d -- those of (u, z_1 .. z_d).
+ *   out_y : S x ldy x ncol floats, summand-major: entry (j, root, c) at out_y[(j * ldy + root) * ncol + c]; ldy >= B, 0 means B.  A chunk of
+ *           roots addresses its slice of one table of ldy roots with the pointer out_y + first root * ncol.
+ *   Definition.  Summand first_h[0] + m is terminal sample m: Y_{g,m} = g_m / mg and, with z, P_m zs; summand first_h[1 + l] + m is sample path
+ *   m of level l: Y_{l,m} and Q_{l,m} -- g_m, P_m, zs, Y and Q as scasml_picard_tree_stderr and scasml_picard_tree_stderr_uz define them.  Under
+ *   rng.world > 1 an entry holds the addends of its summand that THIS rank owns (rng.unit_owner), added in the order of the walk: the sum of
+ *   the ranks' entries is the summand, and their sum over j the rank's partial out_uz to rounding.  EVERY entry of the S x B x ncol block is
+ *   written by every call, 0 where the rank owns nothing of a summand: the caller never clears the table.
+ *   Cost: 4 S B ncol bytes per rank, written once and all-reduced.  At the headline shape (d = 100, quadrature n = rho = 3: S = 37, 16384
+ *   roots) 2.4 MB for u and 245 MB for (u, z), against 6.6 MB of partial sums: the (u, z) form multiplies the collective.
+ *   Refusals, with the codes of scasml_picard_tree_stderr: SCASML_MODE_GENERATE, a null out_y, ncol neither 1 nor 1 + d, ldy below B:
+ *   SCASML_ERR_ARG; rng.flags != 0, plan.mg[n] < 2 or any plan.term[n][l].mc < 2, ldy * ncol >= 2^30 (walk the batch in root chunks):
+ *   SCASML_ERR_UNSUPPORTED.  rng.world >= 1 is accepted.
+ *   plan.n == 0: out_uz is zeros and nothing else is touched (S = 0).  B == 0 does nothing.
+ *
+ * scasml_picard_summands_stderr: the standard errors from the COMPLETED table (summed over the ranks), by the definition of
+ *   scasml_picard_tree_stderr (ncol = 1) and scasml_picard_tree_stderr_uz (ncol = 1 + d): per column and term the deviations from the term's
+ *   first summand, S1 = sum D, S2 = sum D^2, N / (N - 1) (S2 - S1^2 / N); summed over the terms; out_se = sqrt(Var) in float32, Var <= 0 gives 0
+ *   and a NaN passes through.  One thread per (root, column); the table is read once.
+ *   y : as out_y above;  out_se : B x ncol.
+ *   What differs from the fused estimate: the terminal summands enter as g_m / mg and P_m zs (the fused kernels accumulate g_m and P_m and
+ *   scale the closed variance by 1 / mg^2 and zs^2), and a sharded summand is a float32 sum of the ranks' partials, in the order of the
+ *   reduction -- so the two estimates agree to rounding, not bit for bit.  At t = T, where every g_m coincides and every path's weight is 0,
+ *   se_u is exactly 0 at any world; a NaN summand gives NaN, never 0.
+ *   Refusals: a null plan, y (n > 0) or out_se, ncol < 1, ldy below B: SCASML_ERR_ARG; a term of one sample: SCASML_ERR_UNSUPPORTED.
+ *   plan.n == 0: out_se is zeros.  B == 0 does nothing.
+ */
+int32_t scasml_plan_root_summands(const scasml_plan *plan_h, int32_t *first_h, int32_t *count_h);
+int scasml_picard_tree_summands(const scasml_problem *prob_h, const scasml_plan *plan_h, int mode, const float *x_t, int64_t B,
+                                int64_t site_stride, scasml_rng rng, float *points, const float *gp_vals,
+                                float *out_uz, float *out_uhat, float *out_y, int32_t ncol, int64_t ldy, void *stream);
+int scasml_picard_summands_stderr(const scasml_plan *plan_h, const float *y, int64_t B, int64_t ldy, int32_t ncol, float *out_se, void *stream);
+
+/*
  * Staged Picard tree, for equations whose f and g are not in the registry (the driver evaluates them as batched torch
  * functions between launches; solvers/_picard.py).  A level-n solve runs SCASML_MODE_GENERATE of scasml_picard_tree once
  * (its points do not depend on the equation), then stages S = 1 .. n, each computing the (u, z) of every level-S subtree

@@ -76,6 +76,10 @@ SIGNATURES = {
                                             C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "scasml_picard_tree_stderr_uz": (C.c_int, [C.POINTER(Problem), C.POINTER(Plan), C.c_int, C.c_void_p, C.c_int64, C.c_int64, Rng,
                                                C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "scasml_plan_root_summands": (C.c_int32, [C.POINTER(Plan), C.c_void_p, C.c_void_p]),
+    "scasml_picard_tree_summands": (C.c_int, [C.POINTER(Problem), C.POINTER(Plan), C.c_int, C.c_void_p, C.c_int64, C.c_int64, Rng,
+                                              C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int64, C.c_void_p]),
+    "scasml_picard_summands_stderr": (C.c_int, [C.POINTER(Plan), C.c_void_p, C.c_int64, C.c_int64, C.c_int32, C.c_void_p, C.c_void_p]),
     "scasml_picard_stage": (C.c_int, [C.POINTER(Problem), C.POINTER(Plan), C.c_int32, C.c_void_p, C.c_int64, C.c_int64, C.c_int64, Rng,
                                       C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "scasml_picard_stage_stderr": (C.c_int, [C.POINTER(Problem), C.POINTER(Plan), C.c_int32, C.c_void_p, C.c_int64, C.c_int64, C.c_int64, Rng,

@@ -51,7 +51,8 @@ __global__ void debug_jax_normals_kernel(uint32_t k0, uint32_t k1, uint64_t inde
 }
 
 int picard_tree_run(const scasml_problem *prob, const scasml_plan *plan, int mode, const float *x_t, int64_t B, int64_t site_stride, scasml_rng rng,
-                    float *points, const float *gp_vals, float *out_uz, float *out_uhat, float *out_se, SeWanted want_se, void *stream) {
+                    float *points, const float *gp_vals, float *out_uz, float *out_uhat, float *out_se, SeWanted want_se, void *stream,
+                    int32_t ncol, int64_t ldy) {
     if (const int rc = check_batch("picard_tree", prob, plan, B, site_stride)) return rc;
     if (B == 0) return 0;
     if (!x_t) return fail(SCASML_ERR_ARG, "picard_tree: x_t is null");
@@ -70,7 +71,26 @@ int picard_tree_run(const scasml_problem *prob, const scasml_plan *plan, int mod
     if (mode != SCASML_MODE_GENERATE && !out_uz) return fail(SCASML_ERR_ARG, "picard_tree: out_uz is null");
     int np, lp;
     if (first_bad_term(*plan, np, lp)) return fail(SCASML_ERR_ARG, "picard_tree: bad term [%d][%d]", np, lp);
-    if (want_se) {   // scasml_picard_tree_stderr and _stderr_uz: what has no estimate is refused, never answered with a partial number
+    if (want_se == kSummands) {   // scasml_picard_tree_summands: the refusals of the fused estimates but the sharded one -- a table adds across ranks
+        if (mode != SCASML_MODE_MLP && mode != SCASML_MODE_ACCUMULATE)
+            return fail(SCASML_ERR_ARG, "picard_tree_summands: mode %d has no summands (SCASML_MODE_MLP or SCASML_MODE_ACCUMULATE)", mode);
+        if (!out_se) return fail(SCASML_ERR_ARG, "picard_tree_summands: out_y is null");
+        if (ncol != 1 && ncol != prob->d + 1)
+            return fail(SCASML_ERR_ARG, "picard_tree_summands: ncol = %d is neither 1 (u) nor 1 + d = %d (u, z)", ncol, prob->d + 1);
+        if (ldy == 0) ldy = B;
+        if (ldy < B) return fail(SCASML_ERR_ARG, "picard_tree_summands: ldy = %lld below the %lld roots of the call", (long long)ldy, (long long)B);
+        if (ldy > 0x3FFFFFFF / ncol)   // the kernels step from summand to summand by a 32-bit count of bytes
+            return fail(SCASML_ERR_UNSUPPORTED, "picard_tree_summands: ldy * ncol = %lld x %d floats per summand exceed 2^30 - 1: walk the batch in root chunks",
+                        (long long)ldy, ncol);
+        if (rng.flags != 0)
+            return fail(SCASML_ERR_UNSUPPORTED, "picard_tree_summands: rng.flags = %u: SCASML_RNG_COMPAT_CRN shares draws between summands, SCASML_RNG_JAX_STREAM and "
+                        "SCASML_RNG_COMPAT_F16 are parity modes; the summands need flags = 0", rng.flags);
+        if (plan->n > 0 && plan->mg[plan->n] < 2)
+            return fail(SCASML_ERR_UNSUPPORTED, "picard_tree_summands: the terminal term of level %d has %d sample: no estimable variance", plan->n, plan->mg[plan->n]);
+        for (int l = 0; l < plan->n; ++l)
+            if (plan->term[plan->n][l].mc < 2)
+                return fail(SCASML_ERR_UNSUPPORTED, "picard_tree_summands: term [%d][%d] has %d sample path: no estimable variance", plan->n, l, plan->term[plan->n][l].mc);
+    } else if (want_se) {   // scasml_picard_tree_stderr and _stderr_uz: what has no estimate is refused, never answered with a partial number
         if (mode != SCASML_MODE_MLP && mode != SCASML_MODE_ACCUMULATE)
             return fail(SCASML_ERR_ARG, "picard_tree_stderr: mode %d has no estimate (SCASML_MODE_MLP or SCASML_MODE_ACCUMULATE)", mode);
         if (!out_se) return fail(SCASML_ERR_ARG, "picard_tree_stderr: %s is null", want_se == kSeUz ? "out_se_uz" : "out_se");
@@ -91,6 +111,7 @@ int picard_tree_run(const scasml_problem *prob, const scasml_plan *plan, int mod
             if (hipMemsetAsync(out_uz, 0, sizeof(float) * B * (prob->d + 1), s) != hipSuccess)
                 return fail(SCASML_ERR_HIP, "picard_tree: memset failed");
         }
+        if (want_se == kSummands) return 0;   // a level-0 call has no summand: the table has no entry
         if (want_se && hipMemsetAsync(out_se, 0, sizeof(float) * B * (want_se == kSeUz ? prob->d + 1 : 1), s) != hipSuccess)
             return fail(SCASML_ERR_HIP, "picard_tree_stderr: memset failed");
         return 0;
@@ -116,6 +137,10 @@ int picard_tree_run(const scasml_problem *prob, const scasml_plan *plan, int mod
     const dim3 grid((unsigned)blocks);
     // the ladder (picard_tree.hpp) of the unit that holds the kernels: standard errors and the reference's stream have two units each
     const int v = plan->variant, eq = prob->eq_id, n = plan->n;
+    if (want_se == kSummands) {
+        if (ncol == 1) return n > 3 ? launch_tree_summands_deep(a, v, mode, eq, n, grid, s, ldy) : launch_tree_summands(a, v, mode, eq, n, grid, s, ldy);
+        return n > 3 ? launch_tree_summands_uz_deep(a, v, mode, eq, n, grid, s, ldy) : launch_tree_summands_uz(a, v, mode, eq, n, grid, s, ldy);
+    }
     if (want_se == kSeUz) return n > 3 ? launch_tree_stderr_uz_deep(a, v, mode, eq, n, grid, s) : launch_tree_stderr_uz(a, v, mode, eq, n, grid, s);
     if (want_se) return n > 3 ? launch_tree_stderr_deep(a, v, mode, eq, n, grid, s) : launch_tree_stderr(a, v, mode, eq, n, grid, s);
     if (a.jk) return n > 3 ? launch_tree_jax_deep(a, v, mode, eq, n, grid, s) : launch_tree_jax(a, v, mode, eq, n, grid, s);

@@ -5,8 +5,10 @@
 //   picard_tree_stderr.hip / picard_tree_stderr_deep.hip   the kernels that also estimate the standard error of u, levels 1..3 / 4, 5
 //   picard_tree_stderr_uz.hip / picard_tree_stderr_uz_deep.hip   the kernels that estimate the standard errors of u and of every z_i
 //                                                          (picard_se_uz_kernel: the same walker under its SEZ flag), levels 1..3 / 4, 5
+//   picard_tree_summands.hip / picard_tree_summands_deep.hip     the kernels that store the root call's summands of u (picard_sum_kernel:
+//   picard_tree_summands_uz.hip / picard_tree_summands_uz_deep.hip   the walker's SUM flavour) or of (u, z), levels 1..3 / 4, 5
 //   picard_staged.hip                                      the staged walk (its own kernel; shares the lane helpers and the args filler below)
-// Each of the first seven holds ONE call of launch_tree, whose <JAX, SE, N_LO, N_HI, SEZ> decide what that unit compiles -- split so that the build
+// Each of the first eleven holds ONE call of launch_tree, whose <JAX, SE, N_LO, N_HI, SEZ, SUM> decide what that unit compiles -- split so that the build
 // compiles the instantiations in parallel (the JAX-stream kernels inline one Threefry + erf_inv per normal at every site of the unrolled tree).
 #pragma once
 #include <string.h>
@@ -234,10 +236,33 @@ struct SezState {
 template <>
 struct SezState<false> {};
 
-template <int VAR, int MODE, int EQ, bool JAX = false, bool SE = false, bool SEZ = false>
+// The third flavour of the TOP-frame bookkeeping (scasml_picard_tree_summands): where SE / SEZ accumulate a summand into a term's variance,
+// SUM stores it -- into a table that adds across the ranks of a sample-sharded solve, which sums of squares do not.  SUM = 1: the summands
+// of u; 2: those of (u, z_1 .. z_d).  The walk visits the summands in the table's order -- terminal sample 0, 1, ..., then the paths of level
+// 0, 1, ... -- and stores exactly one per visit, so the lane's address of its root's entry steps from summand to summand, and its top bit
+// (no address has it) says that the lane stores nothing: no index arithmetic and no separate predicate are kept across the walk.
+template <int SUM>
+struct SumState {
+    uint64_t at;      // address of the next summand's entry for this lane's root; | kNoStore in a lane that shadows the last root and,
+                      // SUM = 1, in every lane of a group but its first
+    uint32_t stride;  // bytes between consecutive summands: 4 ldy * ncol
+    static constexpr uint64_t kNoStore = 1ull << 63;
+};
+template <>
+struct SumState<0> {};
+template <bool ON>
+struct SumScale {     // what a terminal sample's g and g nrm are stored times: 1 / mg, and the zs of uz()
+    float inv_mg, zs;
+};
+template <>
+struct SumScale<false> {};
+
+template <int VAR, int MODE, int EQ, bool JAX = false, bool SE = false, bool SEZ = false, int SUM = 0>
 struct Walker {
     static_assert(!SEZ || SE, "the standard errors of z come with that of u");
+    static_assert(SUM == 0 || (!SE && !JAX && (MODE == SCASML_MODE_MLP || MODE == SCASML_MODE_ACCUMULATE)), "summands: MLP and ACCUMULATE on the Philox stream, instead of the fused estimate");
     const TreeArgs &a;
+    SumState<SUM> sum; // SUM: where the root call's summands go (TOP frames only)
     SeState<SE> se;    // SE: the variance estimate of the root call's u, summed over its terms (TOP frames only)
     SezState<SEZ> sez; // SEZ: those of this lane's four dims of the root call's z
     float4 mask;       // 1 on this lane's live spatial dims, 0 on padding
@@ -353,13 +378,37 @@ struct Walker {
         return mine;
     }
 
+    // The two parity flags of scasml_rng.  The summand kernels run under flags = 0 only (picard_tree_run refuses anything else), so in them both
+    // are compile-time false: the key-reuse bookkeeping (cbase, c_plus, c_minus) and the float16 branches leave the unrolled tree, and with
+    // them the scalar registers that the table's stores inside the sample loops would otherwise push into a stack slot
+    // (profiles/picard_summands_regs.txt)
+    __device__ __forceinline__ bool crn() const { return SUM != 0 ? false : a.crn != 0; }
+    __device__ __forceinline__ bool f16() const { return SUM != 0 ? false : a.f16 != 0; }
+
+    // SUM: the next summand of the root call, every entry of it: lane 0 of the group stores u's, every lane its live dims of z's.  Lane-predicated
+    // stores only -- no dim_sum inside (group_sum: every lane is active at a sum)
+    __device__ __forceinline__ void put(float yu, float4 yz) {
+        if constexpr (SUM != 0) {
+            if (!(sum.at & SumState<SUM>::kNoStore)) {
+                float *row = reinterpret_cast<float *>(sum.at);
+                if constexpr (SUM == 1) {
+                    row[0] = yu;
+                } else {
+                    if (gl == 0) row[0] = yu;
+                    store_z(row, 4 * (int)gl, a.d, yz);
+                }
+            }
+            sum.at += sum.stride;
+        }
+    }
+
     // Equation.g at time T (equations/equations.py:146-162, 248-261) through the registry; ScaSML.py:61-63 subtracts the surrogate
     __device__ __forceinline__ float g_terminal(float4 XT, float u_hat) const {
         float g = EqDef<EQ>::G(dim_sum(EqDef<EQ>::phi(XT)), a.T);
-        if (a.f16) g = r16(g);                                    // terminal_constraint(...).astype(float16), equations.py:261
+        if (f16()) g = r16(g);                                    // terminal_constraint(...).astype(float16), equations.py:261
         if constexpr (MODE == SCASML_MODE_ACCUMULATE) {
             g -= u_hat;
-            if (a.f16) g = r16(g);                                // float16 - float16 (ScaSML.py:62): a float16 value
+            if (f16()) g = r16(g);                                // float16 - float16 (ScaSML.py:62): a float16 value
         }
         return g;
     }
@@ -371,14 +420,14 @@ struct Walker {
         if constexpr (EqDef<EQ>::kGradSquare) {                   // f(u, sum z, |z|^2): one more sum over the dims (surrogate-free modes only)
             static_assert(MODE != SCASML_MODE_ACCUMULATE, "an f of |z|^2 needs the surrogate's full gradient per site: not in the fused evaluation");
             const float v = EqDef<EQ>::f2(uc, sz, dim_sum(mul4(zc, zc)), a.sigma, fd);
-            return a.f16 ? r16(v) : v;
+            return f16() ? r16(v) : v;
         } else if constexpr (MODE == SCASML_MODE_ACCUMULATE) {
             const float sg = a.sigma * gp.y;
             const float v1 = EqDef<EQ>::f(uc + gp.x, sg + sz, a.sigma, fd), v2 = EqDef<EQ>::f(gp.x, sg, a.sigma, fd);
-            return a.f16 ? r16(r16(v1) - r16(v2)) : v1 - v2;      // generator(...).astype(float16) twice, then float16 - float16 (equations.py:304, ScaSML.py:45-47)
+            return f16() ? r16(r16(v1) - r16(v2)) : v1 - v2;      // generator(...).astype(float16) twice, then float16 - float16 (equations.py:304, ScaSML.py:45-47)
         } else {
             const float v = EqDef<EQ>::f(uc, sz, a.sigma, fd);
-            return a.f16 ? r16(v) : v;
+            return f16() ? r16(v) : v;
         }
     }
 
@@ -478,7 +527,7 @@ struct Walker {
                     // measured slower -- 5.9 against 5.4 ms at n = 4, M = 3 -- the pass is bound by its reads, not its RNG.)
                     float4 xi;
                     if constexpr (JAX) xi = normals_jax(0u, jrow, (uint32_t)mc, (uint32_t)m);
-                    else xi = normals(a.crn && L == 0 ? base + (uint32_t)m : site);
+                    else xi = normals(crn() && L == 0 ? base + (uint32_t)m : site);
                     X = fma4(a.sigma * sD, xi, add4(x, a.mu * D));
                     tk = t + D;
                     wk = tau;
@@ -506,39 +555,41 @@ struct Walker {
                 // contains the same f(u_hat, .).  MLP mode keeps the addend: f(0, 0) = 0 holds for the registered equations, not by construction.
                 if constexpr (!(MODE == SCASML_MODE_ACCUMULATE && L == 0)) {
                     if (mine) {
-                        uz<L, false>(X, tk, base + o, (a.crn && VAR == 0) ? c_plus : base + o, uc, zc, jkrow, jkid);
+                        uz<L, false>(X, tk, base + o, (crn() && VAR == 0) ? c_plus : base + o, uc, zc, jkrow, jkid);
                         if constexpr (MODE != SCASML_MODE_GENERATE) {
                             const float y = f_eval(uc, zc, gp) * (wk * inv_mc);
                             u += y;                              // MLP.py:248
-                            if constexpr (SE && TOP) ym += y;
+                            if constexpr ((SE || SUM != 0) && TOP) ym += y;
                             z = fma4(y * dplus, wvec, z);        // MLP.py:249
-                            if constexpr (SEZ && TOP) zm = fma4(y * dplus, wvec, zm);
+                            if constexpr ((SEZ || SUM == 2) && TOP) zm = fma4(y * dplus, wvec, zm);
                         }
                     }
                 }
                 o += s_l;
                 if constexpr (L > 0) {
                     if (mine_minus) {
-                        uz<L - 1, false>(X, tk, base + o, (a.crn && VAR == 0) ? c_minus : base + o, uc, zc, jkrow, jkid + nsplits<L>());
+                        uz<L - 1, false>(X, tk, base + o, (crn() && VAR == 0) ? c_minus : base + o, uc, zc, jkrow, jkid + nsplits<L>());
                         if constexpr (MODE != SCASML_MODE_GENERATE) {
                             const float y = f_eval(uc, zc, gp) * (wk * inv_mc);
                             u -= y;                              // MLP.py:269
-                            if constexpr (SE && TOP) ym -= y;
+                            if constexpr ((SE || SUM != 0) && TOP) ym -= y;
                             z = fma4(-y * dminus, wvec, z);      // MLP.py:271
-                            if constexpr (SEZ && TOP) zm = fma4(-y * dminus, wvec, zm);
+                            if constexpr ((SEZ || SUM == 2) && TOP) zm = fma4(-y * dminus, wvec, zm);
                         }
                     }
                     o += s_lm;
                 } else if constexpr (MODE == SCASML_MODE_ACCUMULATE) {
                     const float e = gp.z * (wk * inv_mc);        // ScaSML.py:274-280 (l = 0: one addend, mine)
                     u += e;
-                    if constexpr (SE && TOP) ym += e;
+                    if constexpr ((SE || SUM != 0) && TOP) ym += e;
                     z = fma4(e * dminus, wvec, z);
-                    if constexpr (SEZ && TOP) zm = fma4(e * dminus, wvec, zm);
+                    if constexpr ((SEZ || SUM == 2) && TOP) zm = fma4(e * dminus, wvec, zm);
                 }
             }
             if constexpr (SE && TOP) st.add(ym, m == 0);
             if constexpr (SEZ && TOP) zt.add(zm, m == 0);
+            // SUM: after the node loop, which the klast break and both `continue`s leave with what this rank owns of the path (0: nothing)
+            if constexpr (SUM != 0 && TOP) put(ym, zm);
         }
         if constexpr (SE && TOP) se.var += st.close(mc);
         if constexpr (SEZ && TOP) zt.close_into(sez.var, mc, 1.0f);
@@ -581,6 +632,11 @@ struct Walker {
             if constexpr (SE && TOP) st.begin();
             SeTerm4<SEZ && TOP> zt;
             if constexpr (SEZ && TOP) zt.begin();
+            SumScale<SUM != 0 && TOP> ss;
+            if constexpr (SUM != 0 && TOP) {
+                ss.inv_mg = rcp_fast((float)mg);
+                ss.zs = ss.inv_mg * rcp_fast(VAR == 0 ? tau + 1e-6f : tau);
+            }
             for (int m = 0; m < mg; ++m) {                       // MLP.py:175-202
                 const uint32_t site = base + (uint32_t)m;
                 float4 nrm, XT, gpv = f4(0.0f);
@@ -598,7 +654,10 @@ struct Walker {
                             pq.gp[kAhead - 1] = gp_at(site + kAhead);
                         }
                     } else {
-                        if (!owned(TOP)) continue;
+                        if (!owned(TOP)) {
+                            if constexpr (SUM != 0 && TOP) put(0.0f, f4(0.0f));   // another rank's sample: this rank's partial is 0
+                            continue;
+                        }
                         if (readback) XT = load_point(site);
                         gpv = gp_at(site);
                     }
@@ -614,7 +673,10 @@ struct Walker {
                         XT = fma4(vol, nrm, add4(x, drift));
                     }
                 } else {
-                    if (!owned(TOP)) continue;
+                    if (!owned(TOP)) {
+                        if constexpr (SUM != 0 && TOP) put(0.0f, f4(0.0f));
+                        continue;
+                    }
                     if constexpr (JAX) nrm = normals_jax(0u, jrow, (uint32_t)mg, (uint32_t)m);   // every call: split(PRNGKey(0), 1)[0] (MLP.py:167-168, 178)
                     else nrm = normals(cbase + (uint32_t)m);
                     XT = fma4(vol, nrm, add4(x, drift));
@@ -627,6 +689,7 @@ struct Walker {
                     if constexpr (SE && TOP) st.add(g, m == 0);
                     sz = fma4(g, nrm, sz);
                     if constexpr (SEZ && TOP) zt.add(f4_scale(nrm, g), m == 0);   // P_m = g nrm: what the line above adds
+                    if constexpr (SUM != 0 && TOP) put(g * ss.inv_mg, f4_scale(f4_scale(nrm, g), ss.zs));   // g / mg and P_m zs
                 }
             }
             const float inv_mg = rcp_fast((float)mg);
@@ -645,7 +708,7 @@ struct Walker {
                 u = clip1(u, a.clip);
                 z = clip4(z, a.clip);
                 // jnp.clip(...).astype(jnp.float16): MLP.py:274, ScaSML.py:284, MLP_full_history.py:180 -- ScaSML_full_history.py:199 does not cast
-                if (a.f16 && !(VAR == 1 && MODE != SCASML_MODE_MLP)) {
+                if (f16() && !(VAR == 1 && MODE != SCASML_MODE_MLP)) {
                     u = r16(u);
                     z = make_float4(r16(z.x), r16(z.y), r16(z.z), r16(z.w));
                 }
@@ -787,6 +850,58 @@ __global__ __launch_bounds__(256) void picard_se_uz_kernel(const TreeArgs a) {
     }
 }
 
+// The summands of the root call (scasml_picard_tree_summands): the same walk under Walker's SUM flavour, a.out_se carrying the table
+// (TreeArgs stays what it is: a new field would move the kernel arguments of every instance) and ldy its roots per summand.  A kernel template
+// of its own for the reason picard_se_uz_kernel is one, with the same root set-up.
+template <int VAR, int MODE, int N, int EQ, int SUM>
+__global__ __launch_bounds__(256) void picard_sum_kernel(const TreeArgs a, const int64_t ldy) {
+    static_assert(SUM == 1 || SUM == 2, "summands of u, or of (u, z)");
+    normal_table_to_lds();                   // every thread, before any return below
+    const int lane = threadIdx.x & 63;
+    const int wave = (blockIdx.x * (blockDim.x >> 6)) + (threadIdx.x >> 6);
+    const int rpw = 64 >> a.logG;
+    int64_t local = (int64_t)wave * rpw + (lane >> a.logG);
+    const bool valid = local < a.B;
+    if (!valid) local = a.B - 1;  // idle lanes shadow the last root; their stores are masked
+
+    Walker<VAR, MODE, EQ, false, false, false, SUM> w{a};
+    const int ncol = SUM == 2 ? a.d + 1 : 1;
+    w.sum.stride = 4u * (uint32_t)ldy * (uint32_t)ncol;
+    w.gl = (uint32_t)(lane & (a.G - 1));
+    w.sum.at = reinterpret_cast<uint64_t>(a.out_se + local * ncol) | (valid && (SUM == 2 || w.gl == 0) ? 0ull : SumState<SUM>::kNoStore);
+    w.root = a.root0 + (uint32_t)local;
+    w.local = local;
+    w.unit = 0;
+    const int dim0 = 4 * (int)w.gl;
+    w.mask = live_mask(dim0, a.d);
+    w.tmask = make_float4(dim0 + 0 == a.d ? 1.0f : 0.0f, dim0 + 1 == a.d ? 1.0f : 0.0f,
+                          dim0 + 2 == a.d ? 1.0f : 0.0f, dim0 + 3 == a.d ? 1.0f : 0.0f);
+    w.row_lane = dim0 < a.kp;
+    w.row_off4 = (uint32_t)((local * a.kp + (dim0 < a.kp ? dim0 : 0)) >> 2);
+    w.gp_off = (uint32_t)local;
+    const float *row = a.x_t + local * (a.d + 1);
+    float4 x;
+    x.x = dim0 + 0 < a.d ? row[dim0 + 0] : 0.0f;
+    x.y = dim0 + 1 < a.d ? row[dim0 + 1] : 0.0f;
+    x.z = dim0 + 2 < a.d ? row[dim0 + 2] : 0.0f;
+    x.w = dim0 + 3 < a.d ? row[dim0 + 3] : 0.0f;
+    const float t = row[a.d];
+
+    float u;
+    float4 z;
+    w.template uz<N, true>(x, t, 0u, 0u, u, z, (uint64_t)a.root0 + (uint64_t)local, 0u);
+    if (valid) {
+        float *out = a.out_uz + local * (a.d + 1);
+        if (w.gl == 0) {
+            out[0] = u;
+            if constexpr (MODE == SCASML_MODE_ACCUMULATE) {
+                if (a.out_uhat) a.out_uhat[local] = w.gp_at((uint32_t)(a.ppr - 1)).x;
+            }
+        }
+        store_z(out, dim0, a.d, z);
+    }
+}
+
 // ---- the launch ladder ---------------------------------------------------------------------------
 // Which picard_tree_kernel<VAR, MODE, N, EQ, JAX, SE> (SEZ: picard_se_uz_kernel<VAR, MODE, N, EQ>, which exist where the SE kernels do) exist,
 // for either variant and every level of a unit's range -- the one statement of it:
@@ -803,8 +918,8 @@ constexpr bool tree_instance() {
 }
 
 // level n among N .. N_HI (a short compile-time recursion), then the launch
-template <int VAR, int MODE, int EQ, bool JAX, bool SE, int N, int N_HI, bool SEZ>
-int launch_level(const TreeArgs &a, int n, dim3 grid, hipStream_t s) {
+template <int VAR, int MODE, int EQ, bool JAX, bool SE, int N, int N_HI, bool SEZ, int SUM>
+int launch_level(const TreeArgs &a, int n, dim3 grid, hipStream_t s, int64_t ldy) {
     static_assert(!SEZ || SE, "the standard errors of z come with that of u");
     if constexpr (!tree_instance<MODE, EQ, JAX, SE>()) {
         return fail(SCASML_ERR_UNSUPPORTED, "picard_tree: no kernel for mode %d of equation id %d%s%s", MODE, EQ, JAX ? " on the reference's stream" : "",
@@ -814,41 +929,42 @@ int launch_level(const TreeArgs &a, int n, dim3 grid, hipStream_t s) {
         return fail(SCASML_ERR_UNSUPPORTED, "%s level n=%d is not in this translation unit", SE ? "picard_tree_stderr:" : "picard_tree: SCASML_RNG_JAX_STREAM", n);
     } else {
         if (n == N) {
-            if constexpr (SEZ) hipLaunchKernelGGL((picard_se_uz_kernel<VAR, MODE, N, EQ>), grid, dim3(256), 0, s, a);
+            if constexpr (SUM != 0) hipLaunchKernelGGL((picard_sum_kernel<VAR, MODE, N, EQ, SUM>), grid, dim3(256), 0, s, a, ldy);
+            else if constexpr (SEZ) hipLaunchKernelGGL((picard_se_uz_kernel<VAR, MODE, N, EQ>), grid, dim3(256), 0, s, a);
             else hipLaunchKernelGGL((picard_tree_kernel<VAR, MODE, N, EQ, JAX, SE>), grid, dim3(256), 0, s, a);
             return check_launch(SE ? "picard_tree_stderr launch" : "picard_tree launch");
         }
-        return launch_level<VAR, MODE, EQ, JAX, SE, N + 1, N_HI, SEZ>(a, n, grid, s);
+        return launch_level<VAR, MODE, EQ, JAX, SE, N + 1, N_HI, SEZ, SUM>(a, n, grid, s, ldy);
     }
 }
 
-template <int VAR, int MODE, bool JAX, bool SE, int N_LO, int N_HI, bool SEZ>
-int launch_equation(const TreeArgs &a, int eq_id, int n, dim3 grid, hipStream_t s) {
+template <int VAR, int MODE, bool JAX, bool SE, int N_LO, int N_HI, bool SEZ, int SUM>
+int launch_equation(const TreeArgs &a, int eq_id, int n, dim3 grid, hipStream_t s, int64_t ldy) {
     switch (MODE == SCASML_MODE_GENERATE ? SCASML_EQ_GRAD_DEPENDENT_NONLINEAR : eq_id) {   // the one redirection of GENERATE (tree_instance)
-        case SCASML_EQ_GRAD_DEPENDENT_NONLINEAR: return launch_level<VAR, MODE, SCASML_EQ_GRAD_DEPENDENT_NONLINEAR, JAX, SE, N_LO, N_HI, SEZ>(a, n, grid, s);
-        case SCASML_EQ_CUBIC_REACTION_DIFFUSION: return launch_level<VAR, MODE, SCASML_EQ_CUBIC_REACTION_DIFFUSION, JAX, SE, N_LO, N_HI, SEZ>(a, n, grid, s);
+        case SCASML_EQ_GRAD_DEPENDENT_NONLINEAR: return launch_level<VAR, MODE, SCASML_EQ_GRAD_DEPENDENT_NONLINEAR, JAX, SE, N_LO, N_HI, SEZ, SUM>(a, n, grid, s, ldy);
+        case SCASML_EQ_CUBIC_REACTION_DIFFUSION: return launch_level<VAR, MODE, SCASML_EQ_CUBIC_REACTION_DIFFUSION, JAX, SE, N_LO, N_HI, SEZ, SUM>(a, n, grid, s, ldy);
         case SCASML_EQ_QUADRATIC_GRADIENT_REACTION_DIFFUSION:
-            return launch_level<VAR, MODE, SCASML_EQ_QUADRATIC_GRADIENT_REACTION_DIFFUSION, JAX, SE, N_LO, N_HI, SEZ>(a, n, grid, s);
+            return launch_level<VAR, MODE, SCASML_EQ_QUADRATIC_GRADIENT_REACTION_DIFFUSION, JAX, SE, N_LO, N_HI, SEZ, SUM>(a, n, grid, s, ldy);
     }
     return fail(SCASML_ERR_UNSUPPORTED, "picard_tree: unknown equation id %d", eq_id);
 }
 
-template <int VAR, bool JAX, bool SE, int N_LO, int N_HI, bool SEZ>
-int launch_mode(const TreeArgs &a, int mode, int eq_id, int n, dim3 grid, hipStream_t s) {
+template <int VAR, bool JAX, bool SE, int N_LO, int N_HI, bool SEZ, int SUM>
+int launch_mode(const TreeArgs &a, int mode, int eq_id, int n, dim3 grid, hipStream_t s, int64_t ldy) {
     switch (mode) {
-        case SCASML_MODE_MLP: return launch_equation<VAR, SCASML_MODE_MLP, JAX, SE, N_LO, N_HI, SEZ>(a, eq_id, n, grid, s);
-        case SCASML_MODE_GENERATE: return launch_equation<VAR, SCASML_MODE_GENERATE, JAX, SE, N_LO, N_HI, SEZ>(a, eq_id, n, grid, s);
-        case SCASML_MODE_ACCUMULATE: return launch_equation<VAR, SCASML_MODE_ACCUMULATE, JAX, SE, N_LO, N_HI, SEZ>(a, eq_id, n, grid, s);
+        case SCASML_MODE_MLP: return launch_equation<VAR, SCASML_MODE_MLP, JAX, SE, N_LO, N_HI, SEZ, SUM>(a, eq_id, n, grid, s, ldy);
+        case SCASML_MODE_GENERATE: return launch_equation<VAR, SCASML_MODE_GENERATE, JAX, SE, N_LO, N_HI, SEZ, SUM>(a, eq_id, n, grid, s, ldy);
+        case SCASML_MODE_ACCUMULATE: return launch_equation<VAR, SCASML_MODE_ACCUMULATE, JAX, SE, N_LO, N_HI, SEZ, SUM>(a, eq_id, n, grid, s, ldy);
     }
     return fail(SCASML_ERR_ARG, "picard_tree: unknown mode %d", mode);
 }
 
 // A translation unit's kernels are those of the ONE launch_tree<JAX, SE, N_LO, N_HI, SEZ> it instantiates: every variant, mode and equation of
 // tree_instance at levels N_LO .. N_HI.  Refuses an unknown mode, then a level outside the unit's range; launches nothing it refuses.
-template <bool JAX, bool SE, int N_LO, int N_HI, bool SEZ = false>
-int launch_tree(const TreeArgs &a, int variant, int mode, int eq_id, int n, dim3 grid, hipStream_t s) {
-    return variant == 0 ? launch_mode<0, JAX, SE, N_LO, N_HI, SEZ>(a, mode, eq_id, n, grid, s)
-                        : launch_mode<1, JAX, SE, N_LO, N_HI, SEZ>(a, mode, eq_id, n, grid, s);
+template <bool JAX, bool SE, int N_LO, int N_HI, bool SEZ = false, int SUM = 0>
+int launch_tree(const TreeArgs &a, int variant, int mode, int eq_id, int n, dim3 grid, hipStream_t s, int64_t ldy = 0) {
+    return variant == 0 ? launch_mode<0, JAX, SE, N_LO, N_HI, SEZ, SUM>(a, mode, eq_id, n, grid, s, ldy)
+                        : launch_mode<1, JAX, SE, N_LO, N_HI, SEZ, SUM>(a, mode, eq_id, n, grid, s, ldy);
 }
 
 // the reference's own random stream (compat_rng = "jax"): picard_tree_jax.hip (n <= 3) and picard_tree_jax_deep.hip (n = 4, 5)
@@ -860,6 +976,12 @@ int launch_tree_stderr_deep(const TreeArgs &a, int variant, int mode, int eq_id,
 // the kernels that estimate the standard errors of u and of every z_i (SE and SEZ): picard_tree_stderr_uz.hip (n <= 3) and picard_tree_stderr_uz_deep.hip (n = 4, 5)
 int launch_tree_stderr_uz(const TreeArgs &a, int variant, int mode, int eq_id, int n, dim3 grid, hipStream_t s);
 int launch_tree_stderr_uz_deep(const TreeArgs &a, int variant, int mode, int eq_id, int n, dim3 grid, hipStream_t s);
+// the kernels that store the root call's summands (SUM = 1: of u, 2: of (u, z)): picard_tree_summands.hip, picard_tree_summands_uz.hip (n <= 3)
+// and their _deep.hip (n = 4, 5); a.out_se carries the table, ldy its roots per summand
+int launch_tree_summands(const TreeArgs &a, int variant, int mode, int eq_id, int n, dim3 grid, hipStream_t s, int64_t ldy);
+int launch_tree_summands_deep(const TreeArgs &a, int variant, int mode, int eq_id, int n, dim3 grid, hipStream_t s, int64_t ldy);
+int launch_tree_summands_uz(const TreeArgs &a, int variant, int mode, int eq_id, int n, dim3 grid, hipStream_t s, int64_t ldy);
+int launch_tree_summands_uz_deep(const TreeArgs &a, int variant, int mode, int eq_id, int n, dim3 grid, hipStream_t s, int64_t ldy);
 // The fields TreeArgs and StageArgs (picard_staged.hip) have in common: the plan, the batch and its site-major row geometry, the Philox key
 // and the problem's constants.  Returns the roots a wavefront holds, 64 / G, which sizes either grid.
 template <class Args>
@@ -884,10 +1006,16 @@ int fill_common_args(Args &a, const scasml_problem *prob, const scasml_plan *pla
     return 64 / a.G;
 }
 
-// scasml_picard_tree, scasml_picard_tree_stderr and scasml_picard_tree_stderr_uz (want_se selects the kernels and says what out_se holds):
-// one validation, one launch geometry
-enum SeWanted { kSeNone = 0, kSeU = 1, kSeUz = 2 };   // no estimate; B standard errors of u; B rows of 1 + d, those of (u, z)
+// scasml_picard_tree, scasml_picard_tree_stderr, scasml_picard_tree_stderr_uz and scasml_picard_tree_summands (want_se selects the kernels and
+// says what out_se holds): one validation, one launch geometry
+enum SeWanted {
+    kSeNone = 0,    // no estimate
+    kSeU = 1,       // out_se: B standard errors of u
+    kSeUz = 2,      // out_se: B rows of 1 + d, those of (u, z)
+    kSummands = 3   // out_se: the table of the root call's summands, `ncol` columns (1: of u, 1 + d: of (u, z)) and `ldy` roots per summand
+};
 int picard_tree_run(const scasml_problem *prob, const scasml_plan *plan, int mode, const float *x_t, int64_t B, int64_t site_stride, scasml_rng rng,
-                    float *points, const float *gp_vals, float *out_uz, float *out_uhat, float *out_se, SeWanted want_se, void *stream);
+                    float *points, const float *gp_vals, float *out_uz, float *out_uhat, float *out_se, SeWanted want_se, void *stream,
+                    int32_t ncol = 0, int64_t ldy = 0);
 
 }  // namespace scasml

@@ -166,6 +166,25 @@ extern "C" int32_t scasml_plan_deal_units(const scasml_plan *plan_h, int32_t wor
     return (int32_t)units;
 }
 
+// The summands of the root call, term by term in the kernels' order: the mg[n] terminal samples, then the mc sample paths of level 0, 1, ...
+// (a summand groups the units of scasml_plan_deal_units above: one terminal sample, or the q (l = 0) / 2 q (l > 0) addends of one path)
+extern "C" int32_t scasml_plan_root_summands(const scasml_plan *plan_h, int32_t *first_h, int32_t *count_h) {
+    if (!plan_h || plan_h->n < 0 || plan_h->n > SCASML_MAX_LEVEL) return fail(SCASML_ERR_ARG, "plan_root_summands: bad plan (n must be 0..%d)", SCASML_MAX_LEVEL);
+    const int n = plan_h->n;
+    if (n == 0) return 0;
+    int64_t S = 0;
+    for (int j = 0; j <= n; ++j) {
+        const int32_t c = j == 0 ? plan_h->mg[n] : plan_h->term[n][j - 1].mc;
+        if (c < 1) return fail(SCASML_ERR_ARG, "plan_root_summands: term %d of level %d has %d samples", j, n, c);
+        if (first_h) first_h[j] = (int32_t)S;
+        if (count_h) count_h[j] = c;
+        S += c;
+        if (S > 0x7FFFFFFF) return fail(SCASML_ERR_ARG, "plan_root_summands: more than 2^31 - 1 summands");
+    }
+    if (first_h) first_h[n + 1] = (int32_t)S;
+    return (int32_t)S;
+}
+
 extern "C" int scasml_plan_site_kinds(const scasml_plan *plan_h, int32_t rank, int32_t world, const uint8_t *unit_owner_h, uint8_t *kinds_h) {
     if (!plan_h || !kinds_h || plan_h->n < 0 || plan_h->n > SCASML_MAX_LEVEL) return fail(SCASML_ERR_ARG, "plan_site_kinds: bad argument");
     if (world < 1 || rank < 0 || rank >= world) return fail(SCASML_ERR_ARG, "plan_site_kinds: bad rank/world");

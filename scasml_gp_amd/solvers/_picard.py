@@ -182,14 +182,46 @@ class PicardEngine:
                 return False, "term [%d][%d] has %d sample path: no estimable variance" % (n, l, int(plan.term[n][l].mc))
         return True, ""
 
-    def solve(self, n, par, x_t, root0=0, rank=0, world=1, stream_id=None, stderr=False):
+    def root_summands(self, n, par):
+        """S, the number of summands of the root call -- its terminal samples, then the sample paths of every level (scasml_plan_root_summands):
+        the first dimension of the table ``solve(..., summands=...)`` returns.  Host only."""
+        got = int(_lib.load().scasml_plan_root_summands(C.byref(self.plan(n, par)), None, None))
+        if got < 0:
+            raise _lib.ScasmlError("plan_root_summands failed (%d): %s" % (got, _lib.load().scasml_last_error().decode()))
+        return got
+
+    def check_stderr(self, n, par, world=1, staged_ok=True):
+        """Raise what ``solve(..., stderr=...)`` raises for this solver, plan and world, before anything moves; ``solve(..., summands=...)`` makes
+        the same refusals but the sharded one (``world`` = 1 here) and has no staged form (``staged_ok`` = False)."""
+        # A callback equation asks for the staged estimate itself (Equation.staged_stderr); one that does not keeps the refusal such
+        # equations have met since the estimates exist, so that code written against it sees no change
+        if self.callbacks and not staged_ok:
+            raise NotImplementedError("equation %s has torch callbacks: a staged solve stores no summands (it is not sample-sharded)" % type(self.equation).__name__)
+        if self.callbacks and not getattr(self.equation, "staged_stderr", False):
+            raise NotImplementedError("equation %s has torch callbacks: the staged tree estimates standard errors for equations that set "
+                                      "staged_stderr = True (scasml_picard_stage_stderr)" % type(self.equation).__name__)
+        ok, why = self.stderr_supported(n, par)
+        if not ok:
+            raise ValueError("no standard error for n = %d, %s = %d: %s" % (n, "rho" if self.variant == "quad" else "M", par, why))
+        if world != 1 or self.compat_crn or self.compat_f16 or self.compat_rng is not None:
+            raise _lib.ScasmlError("picard_tree_stderr: the estimate needs an unsharded solve (world = 1) on the Philox stream without compat_crn, "
+                                   "compat_f16 or compat_rng: sharded units split a path's addends across ranks, compat_crn shares draws between "
+                                   "summands, the others are parity modes")
+
+    def solve(self, n, par, x_t, root0=0, rank=0, world=1, stream_id=None, stderr=False, summands=None, buffer=None):
         """-> (uz (B, 1+d), u_hat (B,) or None) as torch CUDA tensors, plus was_numpy; with ``stderr`` also, last, the (B,) float32 Monte-Carlo
         standard error of u (scasml_picard_tree_stderr in include/scasml_hip.h: the definition, what it covers and what it leaves out).
         ``stderr="uz"``: last, instead, the (B, 1 + d) float32 standard errors of (u, z_1 .. z_d) (scasml_picard_tree_stderr_uz), column 0
         bit for bit the (B,) result; every refusal of ``stderr=True`` holds for it.  An equation with torch callbacks that sets
         ``staged_stderr = True`` gets the same estimate from the last stage of the staged tree (scasml_picard_stage_stderr); without the
         attribute the solve raises NotImplementedError, as it always has for such equations.
-        The call counter moves as in a plain solve, so calls with and without error bars can be mixed without moving any call's stream."""
+        The call counter moves as in a plain solve, so calls with and without error bars can be mixed without moving any call's stream.
+        ``summands="u"`` or ``"uz"`` (instead of ``stderr``, at ANY ``world``): last, the (S, B, ncol) float32 table of the root call's summands,
+        ncol = 1 or 1 + d (scasml_picard_tree_summands: under sample sharding this rank's partial of every summand, every entry written).  The
+        ranks' tables add; ``finalize_summands`` of the completed table gives the standard errors.  uz is what the plain solve returns.  The
+        refusals are those of ``stderr`` but the sharded one; a callback equation raises NotImplementedError.  ``buffer``: a float32 CUDA
+        tensor of B (1 + d) + S B ncol elements that uz and then the table are views of -- one collective reduces both (parallel.solve_sharded);
+        allocated when None."""
         torch = _lib.require_gpu()
         lib = _lib.load()
         x, was_numpy, x_max = _as_device(x_t, torch)
@@ -200,19 +232,16 @@ class PicardEngine:
         se_uz = isinstance(stderr, str) and stderr == "uz"
         if self.callbacks and world > 1:
             raise NotImplementedError("equation %s has torch callbacks: a staged solve is not sample-sharded" % type(self.equation).__name__)
+        if summands is not None:
+            if summands not in ("u", "uz"):
+                raise ValueError("summands must be None, 'u' or 'uz'")
+            if stderr:
+                raise ValueError("summands= is the sharded form of stderr=: ask for one of them")
+            self.check_stderr(n, par, staged_ok=False)
+        elif buffer is not None:
+            raise ValueError("buffer= holds uz and the table of summands=")
         if stderr:
-            # A callback equation asks for the staged estimate itself (Equation.staged_stderr); one that does not keeps the refusal such
-            # equations have met since the estimates exist, so that code written against it sees no change
-            if self.callbacks and not getattr(self.equation, "staged_stderr", False):
-                raise NotImplementedError("equation %s has torch callbacks: the staged tree estimates standard errors for equations that set "
-                                          "staged_stderr = True (scasml_picard_stage_stderr)" % type(self.equation).__name__)
-            ok, why = self.stderr_supported(n, par)
-            if not ok:
-                raise ValueError("no standard error for n = %d, %s = %d: %s" % (n, "rho" if self.variant == "quad" else "M", par, why))
-            if world != 1 or self.compat_crn or self.compat_f16 or self.compat_rng is not None:
-                raise _lib.ScasmlError("picard_tree_stderr: the estimate needs an unsharded solve (world = 1) on the Philox stream without compat_crn, "
-                                       "compat_f16 or compat_rng: sharded units split a path's addends across ranks, compat_crn shares draws between "
-                                       "summands, the others are parity modes")
+            self.check_stderr(n, par, world)
         plan, prob = self.plan(n, par), self.problem()
         if self.gp is not None and float(getattr(self.gp, "T", self.equation.T)) != float(self.equation.T):
             # the GP folds its terminal time into packed row constants (site kind 3); the tree emits terminal points at the equation's T
@@ -232,7 +261,18 @@ class PicardEngine:
         rng = _lib.Rng(self.seed, self.calls if stream_id is None else stream_id, root0, rank, world, flags, 0, owner, jax_keys)
         if stream_id is None:
             self.calls += 1
-        out = torch.empty((B, d + 1), dtype=torch.float32, device="cuda")
+        table, ncol = None, 0
+        if summands is not None:
+            ncol, S = (d + 1 if summands == "uz" else 1), self.root_summands(n, par)
+            size = B * (d + 1) + S * B * ncol
+            if buffer is None:
+                buffer = torch.empty((size,), dtype=torch.float32, device="cuda")
+            elif not (isinstance(buffer, torch.Tensor) and buffer.is_cuda and buffer.dtype == torch.float32 and buffer.is_contiguous()
+                      and buffer.dim() == 1 and buffer.numel() == size):
+                raise ValueError("buffer must be a contiguous float32 CUDA tensor of %d elements" % size)
+            out, table = buffer[:B * (d + 1)].view(B, d + 1), buffer[B * (d + 1):].view(S, B, ncol)
+        else:
+            out = torch.empty((B, d + 1), dtype=torch.float32, device="cuda")
         # (the staged tree's last stage always fills rows of 1 + d: stderr=True returns their column 0)
         se = torch.empty((B, d + 1) if se_uz or self.callbacks else (B,), dtype=torch.float32, device="cuda") if stderr else None
         s = _lib.stream_ptr()
@@ -243,6 +283,12 @@ class PicardEngine:
             if stderr:
                 self._tree("picard_mlp_stderr", "picard_tree_stderr", prob, plan, _lib.MODE_MLP, x, B, 0, rng, s, out=out, se=se, se_uz=se_uz)
                 return out, None, was_numpy, se
+            if table is not None:
+                if table.shape[0]:
+                    self._tree("picard_mlp_summands", "picard_tree_summands", prob, plan, _lib.MODE_MLP, x, B, 0, rng, s, out=out, table=table)
+                else:                          # n = 0: no summand, uz is zeros
+                    self._tree("picard_mlp", "picard_tree", prob, plan, _lib.MODE_MLP, x, B, 0, rng, s, out=out)
+                return out, None, was_numpy, table
             self._tree("picard_mlp", "picard_tree", prob, plan, _lib.MODE_MLP, x, B, 0, rng, s, out=out)
             self._jax_commit(jax_next, stream_id)
             return out, None, was_numpy
@@ -271,6 +317,9 @@ class PicardEngine:
                 if stderr:
                     self._tree("picard_accumulate_stderr", "picard_tree_stderr(accumulate)", prob, plan, _lib.MODE_ACCUMULATE, xc, nb, stride, rng_c, s,
                                pts=pts, vals=vals, out=ob, uhat=ub, se=se[b0:b0 + nb], se_uz=se_uz)
+                elif table is not None:         # the chunk's slice of the one table: its first root's rows, B roots per summand
+                    self._tree("picard_accumulate_summands", "picard_tree_summands(accumulate)", prob, plan, _lib.MODE_ACCUMULATE, xc, nb, stride, rng_c, s,
+                               pts=pts, vals=vals, out=ob, uhat=ub, table=table, table_root=b0)
                 else:
                     self._tree("picard_accumulate", "picard_tree(accumulate)", prob, plan, _lib.MODE_ACCUMULATE, xc, nb, stride, rng_c, s,
                                pts=pts, vals=vals, out=ob, uhat=ub)
@@ -280,15 +329,23 @@ class PicardEngine:
                 if stderr:
                     se[b0:b0 + nb].zero_()
         self._jax_commit(jax_next, stream_id)
+        if table is not None:
+            return out, uhat, was_numpy, table
         return (out, uhat, was_numpy, se) if stderr else (out, uhat, was_numpy)
 
-    def _tree(self, timer, what, prob, plan, mode, x, nb, stride, rng, s, pts=None, vals=None, out=None, uhat=None, se=None, se_uz=False):
+    def _tree(self, timer, what, prob, plan, mode, x, nb, stride, rng, s, pts=None, vals=None, out=None, uhat=None, se=None, se_uz=False,
+              table=None, table_root=0):
         """One Picard-tree launch over ``nb`` roots under its timer name; ``se`` given: the kernels that also estimate the standard error
-        of u (scasml_picard_tree_stderr) or, with ``se_uz``, of u and every z_i into rows of 1 + d (scasml_picard_tree_stderr_uz).  ``what``
-        names the call in the error a refusal raises."""
+        of u (scasml_picard_tree_stderr) or, with ``se_uz``, of u and every z_i into rows of 1 + d (scasml_picard_tree_stderr_uz).  ``table``
+        given, (S, roots, ncol): the kernels that store the root call's summands (scasml_picard_tree_summands) for the ``nb`` roots from
+        ``table_root`` on.  ``what`` names the call in the error a refusal raises."""
         lib = _lib.load()
         args = (C.byref(prob), C.byref(plan), mode, _lib.ptr(x), nb, stride, rng, _lib.ptr(pts), _lib.ptr(vals), _lib.ptr(out), _lib.ptr(uhat))
-        if se is None:
+        if table is not None:
+            ldy, ncol = table.shape[1], table.shape[2]
+            y = C.c_void_p(table.data_ptr() + 4 * table_root * ncol)
+            _lib.check(self._timed(timer + ("_uz" if ncol > 1 else ""), lambda: lib.scasml_picard_tree_summands(*args, y, ncol, ldy, s)), what)
+        elif se is None:
             _lib.check(self._timed(timer, lambda: lib.scasml_picard_tree(*args, s)), what)
         elif se_uz:
             _lib.check(self._timed(timer + "_uz", lambda: lib.scasml_picard_tree_stderr_uz(*args, _lib.ptr(se), s)), what)
@@ -451,6 +508,21 @@ class PicardEngine:
         round16 = 1 if (self.compat_f16 and not (self.variant == "fh" and self.gp is not None)) else 0
         _lib.check(lib.scasml_clip_round16(_lib.ptr(summed), summed.numel(), self.problem().clip, round16, _lib.stream_ptr()), "clip")
         return summed
+
+    def finalize_summands(self, table, n, par):
+        """(B, ncol) float32 standard errors from the COMPLETED (S, B, ncol) table of ``solve(..., summands=...)`` -- the sum of the ranks'
+        tables of a sample-sharded solve (scasml_picard_summands_stderr: the definition of the fused estimates on the stored summands;
+        equal to them to rounding, not bit for bit)."""
+        torch = _lib.require_gpu()
+        plan = self.plan(n, par)
+        if not (isinstance(table, torch.Tensor) and table.is_cuda and table.dtype == torch.float32 and table.dim() == 3 and table.is_contiguous()
+                and table.shape[0] == self.root_summands(n, par)):
+            raise ValueError("table must be the contiguous float32 CUDA (S = %d, B, ncol) tensor of solve(..., summands=...)" % self.root_summands(n, par))
+        B, ncol = table.shape[1], table.shape[2]
+        se = torch.empty((B, ncol), dtype=torch.float32, device="cuda")
+        _lib.check(self._timed("picard_summands_stderr", lambda: _lib.load().scasml_picard_summands_stderr(
+            C.byref(plan), _lib.ptr(table), B, B, ncol, _lib.ptr(se), _lib.stream_ptr())), "picard_summands_stderr")
+        return se
 
     def evaluation_increment(self, n, par):
         return tables.reference_evaluation_count(self.variant, n, par, self.gp is not None, float(self.equation.T))
