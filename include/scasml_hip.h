@@ -603,6 +603,28 @@ int scasml_gp_variance(const double *L, int64_t Mp, double *rows, int64_t ld, in
 int scasml_gp_sample(const double *Lc, int64_t np, int64_t n, const double *mean, uint64_t seed, int64_t sample0, int64_t S, double *out,
                      int64_t ld_out, void *stream);
 
+/* Added within ABI 7 (additive).  The device pieces of the GP log marginal likelihood and its gradient (csrc/gp_evidence.hip), float64:
+ *   LML = -1/2 z^T alpha - 1/2 log det K_p - M/2 log(2 pi),   K_p = K(a) + nugget I,  alpha = K_p^-1 z,  a = 1 / sigma^2
+ *   dLML/da = 1/2 alpha^T K_a alpha - 1/2 tr(K_p^-1 K_a),     K_a = dK/da
+ * scasml_chol_logdet: out_dev[0] = 2 sum_i log L[i*Mp + i] = log det(L L^T) for the Mp x Mp row-major factor scasml_cholesky leaves.  All Mp rows are summed: identity
+ * padding adds log 1 = 0; a factor made by scasml_cholesky with nugget > 0 carries sqrt(1 + nugget) on its padding rows, whose share
+ * (Mp - M) log(1 + nugget) the caller takes off (models/GP.py does).  One workgroup, one fixed summation order, no atomics. */
+int scasml_chol_logdet(const double *L, int64_t Mp, double *out_dev, void *stream);
+
+/* Added within ABI 7 (additive).  The two contractions of K_a = dK/da the gradient needs, K_a never stored:
+ *   out_dev[0] = sum_ij alpha[i] alpha[j] K_a[i][j],     out_dev[1] = sum_ij A[i*lda + j] K_a[i][j]
+ * over the M x M feature indices of scasml_gp_gram (M = 4 n_dom + n_bdy, the same block order and arguments).  An entry of K is P(ox, oy) kappa
+ * with kappa = exp(-a r^2 / 2); the entry of K_a is (P_a - r^2 P / 2) kappa, evaluated in the epilogue of scasml_gp_gram's 64 x 64 pair tile
+ * (x.y on v_mfma_f64_16x16x4_f64).  A (lda >= M; K_p^-1 as scasml_cholesky_inverse leaves it) is read as a FULL SYMMETRIC matrix: only the pair
+ * tiles on or below the diagonal are walked, the off-diagonal ones counted twice, so A's strict upper triangle beyond the diagonal tiles is not read.
+ * WORKSPACE: out_dev is the caller's and must hold scasml_gp_gram_da_contract_doubles(n_dom, n_bdy) = 2 + 2 T doubles, T = t (t + 1) / 2 the walked
+ * tiles of t = ceil((n_dom + n_bdy) / 64); out_dev[2 ..] receives the workgroups' partial sums.  Per thread, per workgroup, then one fixed-order
+ * pass over the partials; no atomics: the two outputs are the same bits on every run.
+ * Null pointers, d < 1, n_dom < 1, n_bdy < 0 or lda < M: SCASML_ERR_ARG; t > 65535 (scasml_gp_gram's limit): SCASML_ERR_UNSUPPORTED. */
+int64_t scasml_gp_gram_da_contract_doubles(int32_t n_dom, int32_t n_bdy);
+int scasml_gp_gram_da_contract(int32_t d, double a, const float *x_dom, int32_t n_dom, const float *x_bdy, int32_t n_bdy, const double *A, int64_t lda,
+                               const double *alpha, double *out_dev, void *stream);
+
 /* ------------------------------------------------------------------ block-row distributed Gram / Cholesky / solves
  * For collocation sets whose K(phi, phi) does not fit one GPU (BASELINE configs[4]: 1e5 points, M = 350 000, 980 GB float64)
  * the matrix is cut into block rows of SCASML_DIST_BLOCK feature rows, block row i owned by rank i % world and stored as a

@@ -1,0 +1,235 @@
+// The GP log marginal likelihood's device pieces (no counterpart in models/GP.py, which hard-codes sigma and the nugget, :25-26):
+//   LML = -1/2 z^T alpha - 1/2 log det K_p - M/2 log(2 pi),   dLML/da = 1/2 alpha^T K_a alpha - 1/2 tr(K_p^-1 K_a),   K_a = dK/da, a = 1 / sigma^2.
+// (1) scasml_chol_logdet: 2 sum_i log L[i][i] of the factor scasml_cholesky leaves (its identity padding adds log 1 = 0).
+// (2) scasml_gp_gram_da_contract: sum_ij alpha_i alpha_j K_a[i][j] and sum_ij A[i][j] K_a[i][j] in ONE pass of Gram-tile size, K_a never stored.
+//
+// The pass is gp_gram_mfma_kernel's 64 x 64 pair tile (gp_train.hip): x.y on v_mfma_f64_16x16x4_f64, K = d + 1 streamed through LDS, per-point
+// statistics in LDS.  An entry of K is P(ox, oy) kappa with kappa = exp(-a r^2 / 2), so the entry of K_a is (P_a - r^2 P / 2) kappa, P_a = dP/da at
+// fixed geometry.  The epilogue evaluates that table for the pair's up to 16 entries and multiplies each by its A entry and its alpha_i alpha_j (the
+// alphas of the tile's 64 + 64 points sit in LDS beside the statistics).  K_a is symmetric and A is read as a full symmetric matrix (what
+// scasml_cholesky_inverse leaves), so only the tiles on or below the diagonal are walked and the off-diagonal ones count twice.
+//
+// Reduction, one fixed order and no atomics (the two sums are the same bits on every run): a thread adds its entries in the order of its loops
+// (column tile, row tile, fragment register, x-operator, y-operator); a wave combines its lanes by the xor butterfly 32, 16, .., 1; the workgroup's
+// thread 0 adds the four waves in wave order, doubles an off-diagonal tile's pair and writes it to the workgroup's slot of the partials; a second
+// launch of one workgroup adds the slots -- thread t those with index = t mod 256 in rising order, then a halving tree over the 256 threads in LDS.
+#include <math.h>
+
+#include "common.hpp"
+#include "f64_mfma_tile.hpp"
+
+namespace scasml {
+
+constexpr int kEvThreads = 256;
+
+// sum of v over the workgroup's 256 threads in a fixed order: the halving tree in LDS; every thread must call it; the result is thread 0's
+__device__ __forceinline__ double ev_block_sum(double v, double *red) {
+    red[threadIdx.x] = v;
+    __syncthreads();
+#pragma unroll
+    for (int s = kEvThreads / 2; s > 0; s >>= 1) {
+        if ((int)threadIdx.x < s) red[threadIdx.x] += red[threadIdx.x + s];
+        __syncthreads();
+    }
+    return red[0];
+}
+
+__global__ __launch_bounds__(kEvThreads) void chol_logdet_kernel(const double *__restrict__ L, int64_t Mp, double *out) {
+    __shared__ double red[kEvThreads];
+    double s = 0.0;
+    for (int64_t i = threadIdx.x; i < Mp; i += kEvThreads) s += log(L[i * Mp + i]);
+    const double tot = ev_block_sum(s, red);
+    if (threadIdx.x == 0) out[0] = 2.0 * tot;
+}
+
+// which tile of the lower triangle (ti >= tj) is block b, in the order (0,0), (1,0), (1,1), (2,0), ...
+__device__ __forceinline__ void ev_tile_of_block(int64_t b, int &ti, int &tj) {
+    int64_t r = (int64_t)((sqrt(8.0 * (double)b + 1.0) - 1.0) * 0.5);
+    while (r * (r + 1) / 2 > b) --r;
+    while ((r + 1) * (r + 2) / 2 <= b) ++r;
+    ti = (int)r;
+    tj = (int)(b - r * (r + 1) / 2);
+}
+
+__global__ __launch_bounds__(kEvThreads) void gp_gram_da_contract_kernel(int d, double a, const float *x_dom, int n_dom, const float *x_bdy, int n_bdy,
+                                                                         const double *__restrict__ A, int64_t lda, const double *__restrict__ alpha,
+                                                                         double *partials) {
+    constexpr int NT = 2, TBX = 32 * NT, PER = TBX * NB / kEvThreads;
+    extern __shared__ __attribute__((aligned(16))) double smem[];
+    __shared__ double stat[2 * TBX][4];          // (|x|^2 with t, sum of the spatial coordinates, t) of the tile's 64 + 64 points
+    __shared__ double alf[2 * TBX][4];           // alpha at the point's u, Lap, dt, div features (0 where a boundary point has none)
+    __shared__ double wsum[kEvThreads / 64][2];
+    const int N = n_dom + n_bdy;
+    int ti, tj;
+    ev_tile_of_block(blockIdx.x, ti, tj);
+    const int i0 = ti * TBX, j0 = tj * TBX;
+    auto row_of = [&](int p) { return p < n_dom ? x_dom + (int64_t)p * (d + 1) : x_bdy + (int64_t)(p - n_dom) * (d + 1); };
+    {   // two threads per point, even / odd coordinates, combined with one shuffle (gp_gram_mfma_kernel)
+        const int q = threadIdx.x >> 1, par = threadIdx.x & 1;
+        const int p = q < TBX ? i0 + q : j0 + q - TBX;
+        double n = 0.0, sx = 0.0, tt = 0.0;
+        if (p < N) {
+            const float *x = row_of(p);
+            for (int k = par; k < d; k += 2) {
+                const double v = (double)x[k];
+                n = fma(v, v, n);
+                sx += v;
+            }
+            tt = (double)x[d];
+        }
+        n += __shfl_xor(n, 1);
+        sx += __shfl_xor(sx, 1);
+        if (par == 0) {
+            stat[q][0] = fma(tt, tt, n);
+            stat[q][1] = sx;
+            stat[q][2] = tt;
+        }
+        // this thread's two of the point's four alphas: operators par and par + 2
+#pragma unroll
+        for (int h = 0; h < 2; ++h) {
+            const int op = par + 2 * h;
+            double v = 0.0;
+            if (p < N && (op == 0 || p < n_dom)) v = alpha[op == 0 ? (int64_t)p : (int64_t)N + (int64_t)(op - 1) * n_dom + p];
+            alf[q][op] = v;
+        }
+    }   // visible to everyone after the barriers of the K loop below
+    TileAcc<NT> t;
+    mfma_tile_zero(t);
+    const int64_t kend = ((int64_t)d + 1 + NB - 1) / NB * NB;
+    mfma_tile_k_loop<NT>(smem, 0, kend, [&](int64_t kk, double (&ra)[PER], double (&rb)[PER]) {
+#pragma unroll
+        for (int e = 0; e < PER; ++e) {
+            const int idx = threadIdx.x + e * kEvThreads, rr = idx / NB, cc = idx % NB;
+            const int k = (int)kk + cc;
+            ra[e] = (i0 + rr < N && k <= d) ? (double)row_of(i0 + rr)[k] : 0.0;
+            rb[e] = (j0 + rr < N && k <= d) ? (double)row_of(j0 + rr)[k] : 0.0;
+        }
+    }, [] {}, t);
+    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+    const int wr = (wv >> 1) * (16 * NT), wc = (wv & 1) * (16 * NT);
+    const int l15 = lane & 15, l4 = lane >> 4;
+    const double fd = (double)d;
+    double acc_q = 0.0, acc_t = 0.0;             // alpha^T K_a alpha and <A, K_a> over this thread's pairs
+#pragma unroll
+    for (int jt = 0; jt < NT; ++jt) {
+        const int jl = wc + 16 * jt + l15, j = j0 + jl;
+        if (j >= N) continue;
+        const double nj = stat[TBX + jl][0], sj = stat[TBX + jl][1], tjv = stat[TBX + jl][2];
+        const int nops_j = j < n_dom ? 4 : 1;
+#pragma unroll
+        for (int it = 0; it < NT; ++it)
+#pragma unroll
+            for (int e = 0; e < 4; ++e) {
+                const int il = wr + 16 * it + l4 + 4 * e, i = i0 + il;
+                if (i >= N) continue;
+                const double ni = stat[il][0], si = stat[il][1], tiv = stat[il][2];
+                double r2 = fma(-2.0, t.v[it][jt][e], ni + nj);
+                r2 = r2 < 0.0 ? 0.0 : r2;
+                const double rt = tiv - tjv, S = si - sj;
+                double rho2 = fma(-rt, rt, r2);
+                rho2 = rho2 < 0.0 ? 0.0 : rho2;
+                const double kap = exp(-0.5 * a * r2);
+                const int nops_i = i < n_dom ? 4 : 1;
+                // the operator polynomials P(opx, opy) of gp_gram_mfma_kernel (ops: 0 = I, 1 = Lap, 2 = dt, 3 = div) and their derivatives in a
+                const double lap = a * a * rho2 - a * fd, lap_a = 2.0 * a * rho2 - fd;
+                const double aS = a * S, art = a * rt, mix = aS * lap - 2.0 * a * aS;
+                const double mix_a = S * lap + aS * lap_a - 4.0 * aS, tl_a = rt * lap + art * lap_a;
+                const double c3 = 2.0 * fd + 4.0, c2 = fd * fd + 2.0 * fd;
+                const double ll = a * a * a * a * rho2 * rho2 - c3 * a * a * a * rho2 + c2 * a * a;
+                const double ll_a = 4.0 * a * a * a * rho2 * rho2 - 3.0 * c3 * a * a * rho2 + 2.0 * c2 * a;
+                const double P[4][4] = {
+                    {1.0, lap, art, aS},
+                    {lap, ll, art * lap, mix},
+                    {-art, -art * lap, a - art * art, -art * aS},
+                    {-aS, -mix, -art * aS, a * fd - aS * aS}};
+                const double Pa[4][4] = {
+                    {0.0, lap_a, rt, S},
+                    {lap_a, ll_a, tl_a, mix_a},
+                    {-rt, -tl_a, 1.0 - 2.0 * art * rt, -2.0 * art * S},
+                    {-S, -mix_a, -2.0 * art * S, fd - 2.0 * aS * S}};
+                const double h = 0.5 * r2;
+#pragma unroll
+                for (int ox = 0; ox < 4; ++ox) {
+                    if (ox >= nops_i) continue;
+                    const int64_t row = ox == 0 ? i : (int64_t)N + (int64_t)(ox - 1) * n_dom + i;
+                    const double ai = alf[il][ox];
+#pragma unroll
+                    for (int oy = 0; oy < 4; ++oy) {
+                        if (oy >= nops_j) continue;
+                        const int64_t col = oy == 0 ? j : (int64_t)N + (int64_t)(oy - 1) * n_dom + j;
+                        const double ka = (Pa[ox][oy] - h * P[ox][oy]) * kap;
+                        acc_q = fma(ai * alf[TBX + jl][oy], ka, acc_q);
+                        acc_t = fma(A[row * lda + col], ka, acc_t);
+                    }
+                }
+            }
+    }
+#pragma unroll
+    for (int m = 32; m > 0; m >>= 1) {
+        acc_q += __shfl_xor(acc_q, m);
+        acc_t += __shfl_xor(acc_t, m);
+    }
+    if (lane == 0) {
+        wsum[wv][0] = acc_q;
+        wsum[wv][1] = acc_t;
+    }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        const double w = ti == tj ? 1.0 : 2.0;   // the mirrored tile above the diagonal holds the same products
+        partials[2 * (int64_t)blockIdx.x] = w * (((wsum[0][0] + wsum[1][0]) + wsum[2][0]) + wsum[3][0]);
+        partials[2 * (int64_t)blockIdx.x + 1] = w * (((wsum[0][1] + wsum[1][1]) + wsum[2][1]) + wsum[3][1]);
+    }
+}
+
+__global__ __launch_bounds__(kEvThreads) void gp_evidence_sum_kernel(const double *__restrict__ partials, int64_t n, double *out) {
+    __shared__ double red[kEvThreads];
+    double sq = 0.0, st = 0.0;
+    for (int64_t b = threadIdx.x; b < n; b += kEvThreads) {
+        sq += partials[2 * b];
+        st += partials[2 * b + 1];
+    }
+    const double tq = ev_block_sum(sq, red);
+    __syncthreads();
+    const double tt = ev_block_sum(st, red);
+    if (threadIdx.x == 0) {
+        out[0] = tq;
+        out[1] = tt;
+    }
+}
+
+static int64_t ev_tiles(int32_t n_dom, int32_t n_bdy) {
+    const int64_t gt = ((int64_t)n_dom + n_bdy + 63) / 64;
+    return gt * (gt + 1) / 2;
+}
+
+}  // namespace scasml
+
+using namespace scasml;
+
+extern "C" int scasml_chol_logdet(const double *L, int64_t Mp, double *out_dev, void *stream) {
+    if (!L || !out_dev || Mp < 1) return fail(SCASML_ERR_ARG, "chol_logdet: bad argument");
+    hipLaunchKernelGGL(chol_logdet_kernel, dim3(1), dim3(kEvThreads), 0, (hipStream_t)stream, L, Mp, out_dev);
+    return check_launch("chol_logdet launch");
+}
+
+extern "C" int64_t scasml_gp_gram_da_contract_doubles(int32_t n_dom, int32_t n_bdy) {
+    if (n_dom < 1 || n_bdy < 0) return 0;
+    return 2 + 2 * ev_tiles(n_dom, n_bdy);
+}
+
+extern "C" int scasml_gp_gram_da_contract(int32_t d, double a, const float *x_dom, int32_t n_dom, const float *x_bdy, int32_t n_bdy, const double *A,
+                                          int64_t lda, const double *alpha, double *out_dev, void *stream) {
+    if (!x_dom || !A || !alpha || !out_dev || (n_bdy > 0 && !x_bdy)) return fail(SCASML_ERR_ARG, "gp_gram_da_contract: null argument");
+    if (d < 1 || n_dom < 1 || n_bdy < 0 || lda < 4 * (int64_t)n_dom + n_bdy) return fail(SCASML_ERR_ARG, "gp_gram_da_contract: bad sizes");
+    if (((int64_t)n_dom + n_bdy + 63) / 64 > 65535)
+        return fail(SCASML_ERR_UNSUPPORTED, "gp_gram_da_contract: too many collocation points for one launch");
+    const int64_t tiles = ev_tiles(n_dom, n_bdy);      // <= 65535 * 65536 / 2 < 2^31: one grid dimension
+    if (hipFuncSetAttribute(reinterpret_cast<const void *>(gp_gram_da_contract_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
+                            (int)tile_lds_bytes<2>()) != hipSuccess)
+        return fail(SCASML_ERR_HIP, "gp_gram_da_contract: cannot reserve LDS");
+    double *partials = out_dev + 2;
+    hipLaunchKernelGGL(gp_gram_da_contract_kernel, dim3((unsigned)tiles), dim3(kEvThreads), tile_lds_bytes<2>(), (hipStream_t)stream, d, a, x_dom, n_dom,
+                       x_bdy, n_bdy, A, lda, alpha, partials);
+    hipLaunchKernelGGL(gp_evidence_sum_kernel, dim3(1), dim3(kEvThreads), 0, (hipStream_t)stream, partials, tiles, out_dev);
+    return check_launch("gp_gram_da_contract launch");
+}

@@ -10,6 +10,8 @@ What runs where:
   are block-wise elementwise expressions (b is affine except for the product z1*z5 in F, :705-719), so
   no autodiff and no per-iteration GEMM is needed ........... scasml_gp_newton_b / _gemv / _gp_newton_system
 * predict / compute_gradient / compute_PDE_loss (:653-687, 746-769) .. scasml_gp_eval, scasml_gp_gradient
+* log marginal likelihood, its gradient in (log sigma, log nugget) and a fit of the two (no counterpart: :25-26 hard-code them; compat=None only)
+  .............................................................. scasml_chol_logdet, scasml_gp_gram_da_contract
 
 Two surrogates (``compat``):
 * ``None``: the operators the reference documents -- exact Laplacian features, no float16 rounding.
@@ -52,6 +54,66 @@ def _f16_exact(*xs):
     import torch
     ts = (x if isinstance(x, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(x)) for x in xs)
     return all(bool((t.half().to(t.dtype) == t).all()) for t in ts)
+
+
+def _maximize_bounded(fun, x0, lo, hi, gtol, max_iter):
+    """Maximise ``fun`` over the box lo <= x <= hi in a handful of variables (GP.optimize_hyperparameters: one or two log-parameters).
+    fun(x) -> (value, gradient), or None where the function is undefined (taken as a rejected trial point).
+
+    Projected BFGS on -fun: variables that sit on a bound with the gradient pushing outward are held, the others move along -H g (the first step
+    and every restart: steepest ascent), no step longer than 1 in any variable (a factor e in a log-parameter), trial points clipped into the
+    box, Armijo backtracking with a safeguarded quadratic fit, the inverse-Hessian update skipped when the curvature along the step is not
+    positive.  Stops when max |g| over the variables not held is <= gtol (converged), after max_iter iterations or when the line search finds
+    no increase.  Returns (x, value, gradient, evaluations, iterations, converged)."""
+    lo, hi = np.asarray(lo, dtype=np.float64), np.asarray(hi, dtype=np.float64)
+    x = np.clip(np.asarray(x0, dtype=np.float64), lo, hi)
+    res = fun(x)
+    if res is None:
+        raise ValueError("the function is undefined at the start")
+    f, g = -float(res[0]), -np.asarray(res[1], dtype=np.float64)
+    evals, iters, H = 1, 0, None
+    while True:
+        free = ~(((x <= lo) & (g > 0.0)) | ((x >= hi) & (g < 0.0)))
+        if not free.any() or float(np.abs(g[free]).max()) <= gtol:
+            return x, -f, -g, evals, iters, True
+        if iters >= max_iter:
+            return x, -f, -g, evals, iters, False
+        iters += 1
+        p = -(H @ g) if H is not None else -g
+        p[~free] = 0.0
+        if H is None or float(p @ g) >= 0.0:                 # no model yet, or not a descent direction: restart along the projected gradient
+            H = None
+            p = np.where(free, -g, 0.0)
+        big = float(np.abs(p).max())
+        if big > 1.0:
+            p = p / big
+        t, accepted = 1.0, None
+        for _ in range(30):
+            xn = np.clip(x + t * p, lo, hi)
+            step = xn - x
+            if not step.any():
+                break
+            res = fun(xn)
+            evals += 1
+            slope = float(g @ step)
+            if res is not None and -float(res[0]) <= f + 1e-4 * slope:
+                accepted = (xn, -float(res[0]), -np.asarray(res[1], dtype=np.float64))
+                break
+            # minimiser of the parabola through f, slope and the rejected value, kept inside [0.1 t, 0.5 t]
+            tq = 0.5 * t if res is None else -slope * t / (2.0 * (-float(res[0]) - f - slope))
+            t = min(max(tq, 0.1 * t), 0.5 * t) if np.isfinite(tq) and tq > 0.0 else 0.5 * t
+        if accepted is None:
+            return x, -f, -g, evals, iters, False
+        xn, fn, gn = accepted
+        s, y = xn - x, gn - g
+        sy = float(s @ y)
+        if sy > 1e-12 * float(np.linalg.norm(s) * np.linalg.norm(y)):
+            if H is None:
+                H = np.eye(len(x)) * (sy / float(y @ y))
+            rho = 1.0 / sy
+            V = np.eye(len(x)) - rho * np.outer(s, y)
+            H = V @ H @ V.T + rho * np.outer(s, s)
+        x, f, g = xn, fn, gn
 
 
 class GP(object):
@@ -164,7 +226,11 @@ class GP(object):
     @property
     def a(self):
         """The kernel's scale a = 1 / sigma^2 (models/GP.py:25, 41-43)."""
-        return 1.0 / float(self.sigma) ** 2
+        return self._a_of(self.sigma)
+
+    @staticmethod
+    def _a_of(sigma):
+        return 1.0 / float(sigma) ** 2
 
     def _fp16_in_range(self, x_bound):
         """The fp16 planes' range rule: 0.72 a |x|^2 with |x_k| <= x_bound (0 = the default 2) stays below 3e4 (scasml_gp_model.x_bound)."""
@@ -317,7 +383,7 @@ class GP(object):
         if info != 0 or bool(torch.isnan(L).any()):
             raise ValueError("Cholesky decomposition resulted in NaN values.")        # models/GP.py:264-265
         self._L_pad = L
-        self._L_made_for = (xd, xb, self.nugget)           # predict_variance: the factor belongs to these collocation tensors
+        self._L_made_for = (xd, xb, self.nugget, self.sigma)   # predict_variance: the factor belongs to these collocation tensors, this noise and scale
         self.cholesky_phi_phi_perturb = L[:M, :M]
         if as_coded:                       # kernel_phi_phi_perturb.astype(float16) (:268): the entries are float16 already, the diagonal moves
             _lib.check(lib.scasml_round16_diag(_lib.ptr(K), M, M, float(self.nugget), s), "round16_diag")
@@ -519,7 +585,7 @@ class GP(object):
         return {"n_input": np.int64(self.n_input), "x_t_domain": np.asarray(self.x_t_domain),
                 "x_t_boundary": np.asarray(self.x_t_boundary), "right_vector": np.asarray(self.right_vector),
                 "loss_history": np.asarray(getattr(self, "loss_history", []), dtype=np.float64),
-                "nugget": np.float64(self.nugget), "T": np.float64(self.T), "compat": np.str_(self.compat or ""), "f16_graph": np.bool_(self.f16_graph),
+                "nugget": np.float64(self.nugget), "sigma": np.float64(self.sigma), "T": np.float64(self.T), "compat": np.str_(self.compat or ""), "f16_graph": np.bool_(self.f16_graph),
                 # the float16 op sequence is only taken on float16 collocation points; otherwise the fit silently used one rounding per entry
                 "f16_graph_effective": np.bool_(self._f16_graph_rows(True)),
                 "laplacian_idx": np.asarray(self.laplacian_idx if self.laplacian_idx is not None else [], dtype=np.int32)}
@@ -536,9 +602,12 @@ class GP(object):
         if bool(state.get("f16_graph", False)) != bool(self.f16_graph):
             raise ValueError("state was trained with f16_graph=%s: construct the GP with the same flag" % bool(state.get("f16_graph", False)))
         self.nugget = float(state["nugget"])
+        if "sigma" in state:                                # states saved before the scale was carried keep this object's value
+            self.sigma = float(state["sigma"])
         if "T" in state and float(state["T"]) != float(self.T):
             raise ValueError("state was trained with terminal time T = %g, this GP's equation has T = %g" % (float(state["T"]), float(self.T)))
         self.loss_history = list(np.asarray(state["loss_history"], dtype=np.float64))
+        self._sol = None                                    # the Newton unknowns of an earlier GPsolver do not belong to the loaded state
         self.load_right_vector(state["x_t_domain"], state["x_t_boundary"], state["right_vector"])
         return self
 
@@ -567,7 +636,8 @@ class GP(object):
         if getattr(self, "_xd", None) is None:
             raise _lib.ScasmlError("no collocation points yet: call GPsolver / kernel_phi_phi / load_right_vector first")
         made_for = getattr(self, "_L_made_for", None)
-        if getattr(self, "_L_pad", None) is None or made_for is None or made_for[0] is not self._xd or made_for[1] is not self._xb or made_for[2] != self.nugget:
+        if (getattr(self, "_L_pad", None) is None or made_for is None or made_for[0] is not self._xd or made_for[1] is not self._xb
+                or made_for[2] != self.nugget or made_for[3] != self.sigma):
             self.kernel_phi_phi(self.x_t_domain, self.x_t_boundary)
         return self._L_pad
 
@@ -603,6 +673,188 @@ class GP(object):
         '''(n, 1) float64 posterior standard deviation sqrt(max(predict_variance, 0)).'''
         var = self.predict_variance(x_t_infer)
         return np.sqrt(np.maximum(var, 0.0)) if isinstance(var, np.ndarray) else var.clamp_min(0.0).sqrt()
+
+    # log marginal likelihood, its gradient and a fit of (sigma, nugget) to it (no counterpart in models/GP.py, which hard-codes both, :25-26)
+    def _evidence_ready(self):
+        if self.compat == "reference":
+            raise ValueError("the log marginal likelihood needs compat=None: the as-coded matrix is not the Gram of one kernel and has no derivative in a")
+        if getattr(self, "_xd", None) is None:
+            raise _lib.ScasmlError("no collocation points yet: call GPsolver / kernel_phi_phi / load_right_vector first")
+
+    def _gram_at(self, a):
+        """K(a) of the documented operators on the held collocation points, (M, M) float64 on the device, nothing added to the diagonal."""
+        torch = _lib.require_gpu()
+        M = self.phi_dim
+        K = torch.empty((M, M), dtype=torch.float64, device="cuda")
+        _lib.check(_lib.load().scasml_gp_gram(self.d, float(a), _lib.ptr(self._xd), self.N_domain, _lib.ptr(self._xb), self.N_boundary, _lib.ptr(K),
+                                              _lib.stream_ptr()), "gp_gram")
+        return K
+
+    def _evidence_z(self, z):
+        """The M feature values the likelihood is taken of, float64 on the device: the caller's, else b(sol) of the fit, else K_p right_vector."""
+        torch = _lib.require_gpu()
+        lib = _lib.load()
+        N, Nb, M = self.N_domain, self.N_boundary, self.phi_dim
+        s = _lib.stream_ptr()
+        if z is not None:
+            zt = z.detach() if isinstance(z, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(np.asarray(z, dtype=np.float64)))
+            zt = zt.to(device="cuda", dtype=torch.float64).reshape(-1).contiguous()
+            if zt.numel() != M:
+                raise ValueError("z has %d entries, expected 4 N_domain + N_boundary = %d" % (zt.numel(), M))
+            return zt
+        sol = getattr(self, "_sol", None)
+        if sol is not None and sol.numel() == 3 * N:                   # b(sol) = [z1, g, z3, F(sol), z5], as GPsolver's last residual built it
+            g = torch.as_tensor(np.asarray(self.bdy_g(self.x_t_boundary), dtype=np.float64), device="cuda").contiguous()
+            b = torch.empty(M, dtype=torch.float64, device="cuda")
+            _lib.check(lib.scasml_gp_newton_b(int(self.equation.eq_id), int(self.d), float(self.equation.sigma()), float(self.equation.mu()),
+                                              _lib.ptr(sol.contiguous()), _lib.ptr(g), N, Nb, _lib.ptr(b), s), "gp_newton_b")
+            return b
+        if self.right_vector is None:
+            raise _lib.ScasmlError("no feature values: pass z, or fit (GPsolver) or load a right_vector first")
+        rv = torch.from_numpy(np.ascontiguousarray(np.asarray(self.right_vector, dtype=np.float64).reshape(-1))).cuda()
+        K = self._gram_at(self.a)
+        out = torch.empty(M, dtype=torch.float64, device="cuda")
+        _lib.check(lib.scasml_gemv(_lib.ptr(K), M, M, _lib.ptr(rv), _lib.ptr(out), s), "gemv")
+        return out.add_(rv, alpha=float(self.nugget))                  # z = K_p right_vector
+
+    def _evidence_factor(self, sigma, nugget):
+        """The padded factor of K(1 / sigma^2) + nugget I: the cached one at the object's own values, else a fresh one that is not kept (None when
+        the matrix is not positive definite there).  A fresh one is kernel_phi_phi's own device work: the same bits a GP holding these values gets."""
+        torch = _lib.require_gpu()
+        if sigma == self.sigma and nugget == self.nugget:
+            return self._variance_factor()
+        L, info = self._factor_padded(self._gram_at(self._a_of(sigma)), nugget, "cholesky(evidence)")
+        return None if info != 0 or bool(torch.isnan(L).any()) else L
+
+    def _evidence(self, zt, sigma, nugget, return_grad):
+        """(LML, (dLML/dlog sigma, dLML/dlog nugget) or None) at (sigma, nugget) for the device vector zt; None where K_p is not positive definite."""
+        torch = _lib.require_gpu()
+        lib = _lib.load()
+        M = self.phi_dim
+        s = _lib.stream_ptr()
+        L = self._evidence_factor(sigma, nugget)
+        if L is None:
+            return None
+        Mp = L.shape[0]
+        y = torch.zeros((Mp, 1), dtype=torch.float64, device="cuda")
+        y[:M, 0] = zt
+        _lib.check(lib.scasml_trsm_lower(_lib.ptr(L), Mp, _lib.ptr(y), 1, 0, s), "trsm")           # y = L^-1 z:  z^T alpha = |y|^2
+        out = torch.zeros(8, dtype=torch.float64, device="cuda")      # [log det, |y|^2, alpha^T K_a alpha, <A, K_a>, tr A, |alpha|^2]
+        _lib.check(lib.scasml_chol_logdet(_lib.ptr(L), Mp, _lib.ptr(out), s), "chol_logdet")
+        # the factor of the identity-padded K + nugget I has sqrt(1 + nugget), not 1, on its padding rows (scasml_cholesky adds the nugget to the
+        # whole diagonal): their share of the sum is taken off again
+        out[0] -= 2.0 * torch.log(L.diagonal()[M:]).sum()
+        out[1] = torch.dot(y[:, 0], y[:, 0])
+        if return_grad:
+            a = self._a_of(sigma)
+            A = torch.empty((Mp, Mp), dtype=torch.float64, device="cuda")                          # K_p^-1
+            _lib.check(lib.scasml_cholesky_inverse(_lib.ptr(L), Mp, _lib.ptr(A), s), "cholesky_inverse")
+            alpha = torch.empty(M, dtype=torch.float64, device="cuda")
+            _lib.check(lib.scasml_gemv(_lib.ptr(A), M, Mp, _lib.ptr(zt), _lib.ptr(alpha), s), "gemv")
+            work = torch.empty(int(lib.scasml_gp_gram_da_contract_doubles(self.N_domain, self.N_boundary)), dtype=torch.float64, device="cuda")
+            _lib.check(lib.scasml_gp_gram_da_contract(self.d, a, _lib.ptr(self._xd), self.N_domain, _lib.ptr(self._xb), self.N_boundary, _lib.ptr(A), Mp,
+                                                      _lib.ptr(alpha), _lib.ptr(work), s), "gp_gram_da_contract")
+            out[2:4] = work[:2]
+            out[4] = A.diagonal()[:M].sum()
+            out[5] = torch.dot(alpha, alpha)
+        logdet, quad, q_a, t_a, tr_a, aa = out.cpu().numpy()[:6].tolist()
+        value = -0.5 * quad - 0.5 * logdet - 0.5 * M * float(np.log(2.0 * np.pi))
+        if not return_grad:
+            return value, None
+        d_a = 0.5 * q_a - 0.5 * t_a
+        d_eta = 0.5 * aa - 0.5 * tr_a
+        return value, (-2.0 * a * d_a, float(nugget) * d_eta)
+
+    def log_marginal_likelihood(self, z=None, return_grad=False, sigma=None, nugget=None):
+        '''log p(z | sigma, nugget) of the M = 4 N_domain + N_boundary feature values z under the documented-operator prior (compat=None only; the
+        as-coded matrix is not the Gram of one kernel: ValueError), on the collocation points this object holds:
+
+            LML = -1/2 z^T alpha - 1/2 log det K_p - M/2 log(2 pi),    K_p = K(a) + nugget I,  a = 1 / sigma^2,  alpha = K_p^-1 z.
+
+        Returns a float; with return_grad=True ``(value, {"log_sigma": dLML/dlog sigma, "log_nugget": dLML/dlog nugget})``, where
+        dLML/dlog sigma = -2 a dLML/da, dLML/da = 1/2 alpha^T K_a alpha - 1/2 tr(K_p^-1 K_a) with K_a = dK/da, and dLML/dlog nugget =
+        nugget (1/2 alpha^T alpha - 1/2 tr K_p^-1).
+
+        z: an array of M values; None: the fit's own feature vector b(sol) = [z1, g, z3, F(sol), z5] after GPsolver (rebuilt from the Newton unknowns
+        by scasml_gp_newton_b), else K_p right_vector after load_state_dict / load_right_vector (the two agree to rounding).  sigma / nugget: evaluate
+        at other hyperparameters without changing the object or its cached factor; at the object's own values the cached factor is reused.
+
+        Cost.  Value: one Gram and one Cholesky (none with the cached factor), one triangular solve, scasml_chol_logdet.  Gradient, in addition:
+        scasml_cholesky_inverse, one scasml_gemv, scasml_gp_gram_da_contract (one pass of Gram-tile size on the FP64 matrix cores, K_a never stored),
+        a trace and a dot product.  The gradient holds TWO Mp x Mp float64 matrices on the device, the factor and K_p^-1 (Mp = M rounded up to 32).
+        Every sum has a fixed order: two calls return the same bits.'''
+        self._evidence_ready()
+        sigma = self.sigma if sigma is None else float(sigma)
+        nugget = self.nugget if nugget is None else float(nugget)
+        if not (sigma > 0.0 and nugget > 0.0):
+            raise ValueError("sigma and nugget must be positive")
+        res = self._evidence(self._evidence_z(z), sigma, nugget, bool(return_grad))
+        if res is None:
+            raise ValueError("K(sigma = %g) + %g I is not positive definite in float64" % (sigma, nugget))
+        value, grad = res
+        return (value, {"log_sigma": grad[0], "log_nugget": grad[1]}) if return_grad else value
+
+    def optimize_hyperparameters(self, z=None, which=("sigma", "nugget"), bounds=None, gtol=None, max_iter=50):
+        '''Maximise log_marginal_likelihood(z; sigma, nugget) at FIXED z over the log of the parameters named in ``which`` (type-II maximum likelihood).
+
+        A bounded BFGS iteration on the host in at most two variables (_maximize_bounded; every evaluation is one device value + gradient).  bounds:
+        {"sigma": (lo, hi), "nugget": (lo, hi)}; default sigma within a factor 8 of its current value, nugget in [1e-6, 1]; a start outside is moved
+        onto the bound.  Stops when max |dLML/dlog theta| <= gtol (default 1e-4 M) over the variables not held at a bound by the gradient, or after
+        max_iter iterations.
+
+        When it converges it sets self.sigma and self.nugget, refactors, sets right_vector = K_p^-1 z and re-packs, so predict, predict_variance and
+        the solvers see the new model at once -- for a linear problem this is the complete refit; for the nonlinear fit alternate
+        GPsolver -> optimize_hyperparameters() -> GPsolver by hand (INTEGRATION.md).  When it does not, the object is left as it was.
+        Returns {"sigma_start", "nugget_start", "lml_start", "sigma", "nugget", "lml", "grad": {"log_sigma", "log_nugget"}, "evaluations",
+        "iterations", "converged"}: the best point found, installed or not.'''
+        torch = _lib.require_gpu()
+        lib = _lib.load()
+        self._evidence_ready()
+        which = (which,) if isinstance(which, str) else tuple(which)
+        if not which or len(set(which)) != len(which) or any(w not in ("sigma", "nugget") for w in which):
+            raise ValueError("which must name 'sigma', 'nugget' or both")
+        zt = self._evidence_z(z)
+        M = self.phi_dim
+        start = {"sigma": float(self.sigma), "nugget": float(self.nugget)}
+        box = {"sigma": (start["sigma"] / 8.0, start["sigma"] * 8.0), "nugget": (1e-6, 1.0)}
+        for k, (lo, hi) in (bounds or {}).items():
+            if k not in box or not 0.0 < float(lo) <= float(hi):
+                raise ValueError("bounds: {'sigma': (lo, hi), 'nugget': (lo, hi)} with 0 < lo <= hi")
+            box[k] = (float(lo), float(hi))
+        gtol = 1e-4 * M if gtol is None else float(gtol)
+        lo = np.log([box[w][0] for w in which])
+        hi = np.log([box[w][1] for w in which])
+
+        def fun(x):
+            p = dict(start)
+            p.update({w: float(np.exp(v)) for w, v in zip(which, x)})
+            res = self._evidence(zt, p["sigma"], p["nugget"], True)
+            if res is None:
+                return None
+            return res[0], np.array([res[1][0 if w == "sigma" else 1] for w in which])
+
+        lml_start = self._evidence(zt, start["sigma"], start["nugget"], False)
+        x, val, grad, evals, iters, converged = _maximize_bounded(fun, np.log([start[w] for w in which]), lo, hi, gtol, int(max_iter))
+        best = dict(start)
+        best.update({w: float(np.exp(v)) for w, v in zip(which, x)})
+        full = self._evidence(zt, best["sigma"], best["nugget"], True)          # both derivatives at the returned point, held parameters included
+        report = {"sigma_start": start["sigma"], "nugget_start": start["nugget"], "lml_start": None if lml_start is None else lml_start[0],
+                  "sigma": best["sigma"], "nugget": best["nugget"], "lml": val, "grad": {"log_sigma": full[1][0], "log_nugget": full[1][1]},
+                  "evaluations": evals + 2, "iterations": iters, "converged": bool(converged)}
+        if not converged:
+            return report
+        self.sigma, self.nugget = best["sigma"], best["nugget"]
+        L = self._variance_factor()                                     # refactors: the cache key holds both parameters
+        Mp = L.shape[0]
+        rv = torch.zeros((Mp, 1), dtype=torch.float64, device="cuda")
+        rv[:M, 0] = zt
+        s = _lib.stream_ptr()
+        _lib.check(lib.scasml_trsm_lower(_lib.ptr(L), Mp, _lib.ptr(rv), 1, 0, s), "trsm")
+        _lib.check(lib.scasml_trsm_lower(_lib.ptr(L), Mp, _lib.ptr(rv), 1, 1, s), "trsm^T")
+        rv = rv[:M, 0].contiguous()
+        self.right_vector = rv.cpu().numpy()[:, None]
+        self._pack(rv)
+        return report
 
     # joint posterior (no counterpart in models/GP.py): covariance between evaluation points and draws from N(mean, cov)
     def _cross_rows(self, x_dom, x_bdy, op, xi, out, ld, r16):
