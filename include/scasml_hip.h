@@ -625,6 +625,31 @@ int64_t scasml_gp_gram_da_contract_doubles(int32_t n_dom, int32_t n_bdy);
 int scasml_gp_gram_da_contract(int32_t d, double a, const float *x_dom, int32_t n_dom, const float *x_bdy, int32_t n_bdy, const double *A, int64_t lda,
                                const double *alpha, double *out_dev, void *stream);
 
+/* LOO: added within ABI 7 (additive).  Feature rows [row0, row0 + nrows) x columns [0, ncols) of K_a = dK/da into out (row-major, leading dimension
+ * ld >= ncols): the twin of scasml_gp_gram_rows -- the same arguments, block order [u(dom), u(bdy), Lap(dom), dt(dom), div(dom)], 64 x 64 FP64-MFMA pair
+ * tile and refusals -- with the entries (P_a - r^2 P / 2) kappa that scasml_gp_gram_da_contract contracts (one statement of the table serves both,
+ * csrc/gp_gram_da_table.hpp).  An entry is a function of its pair of points alone, bit for bit: it does not depend on row0, nrows or ncols.
+ * More than 65535 point tiles of 64, or row tiles per call: SCASML_ERR_UNSUPPORTED, before anything is launched. */
+int scasml_gp_gram_da_rows(int32_t d, double a, const float *x_dom, int32_t n_dom, const float *x_bdy, int32_t n_bdy, int64_t row0, int32_t nrows,
+                           int64_t ncols, double *out, int64_t ld, void *stream);
+
+/* LOO: added within ABI 7 (additive).  What the gradient of the leave-one-out predictive log-likelihood in a = 1 / sigma^2 needs of K_a (Rasmussen &
+ * Williams 5.4.2; csrc/gp_loo.hip), for every feature i < M = 4 n_dom + n_bdy:
+ *   q_out[i] = sum_jk A[i*lda + j] K_a[j][k] A[i*lda + k]  ( = [A K_a A]_ii ),     v_out[i] = sum_j K_a[i][j] alpha[j]
+ * A (lda >= M; K_p^-1 as scasml_cholesky_inverse leaves it) is read as a FULL SYMMETRIC matrix, its first M rows and columns only.  K_a is walked in
+ * panels of panel_rows feature rows (a multiple of 64; 0: the library's default, 512; never more than M rounded up to 64): a panel is written by
+ * scasml_gp_gram_da_rows' kernel, v of its rows is one row reduction, and a 64 x 64 tile kernel on v_mfma_f64_16x16x4_f64 forms A[I, :] panel^T with
+ * K dimension M and, in its epilogue, multiplies by A[I, panel rows] and sums along the row instead of storing the product.
+ * WORKSPACE: work is the caller's and must hold scasml_gp_loo_da_doubles(n_dom, n_bdy, panel_rows) = (panel rows + ceil(M / 64)) M doubles: the panel,
+ * then one partial sum per (64-column tile, row).  Nothing else is allocated and no second M x M matrix exists.
+ * No atomics; every sum has one fixed order (per lane, 16-lane butterfly, two waves in order, then the column tiles in rising order), and a column
+ * tile is the same 64 features for every panel_rows: q_out and v_out are the same bits on every run AND for every panel_rows.
+ * Null pointers, d < 1, n_dom < 1, n_bdy < 0, lda < M, panel_rows negative or not a multiple of 64: SCASML_ERR_ARG; more than 65535 point tiles of
+ * 64: SCASML_ERR_UNSUPPORTED; all before anything is launched.  scasml_gp_loo_da_doubles returns 0 for sizes the entry refuses. */
+int64_t scasml_gp_loo_da_doubles(int32_t n_dom, int32_t n_bdy, int32_t panel_rows);
+int scasml_gp_loo_da(int32_t d, double a, const float *x_dom, int32_t n_dom, const float *x_bdy, int32_t n_bdy, const double *A, int64_t lda,
+                     const double *alpha, int32_t panel_rows, double *q_out, double *v_out, double *work, void *stream);
+
 /* ------------------------------------------------------------------ block-row distributed Gram / Cholesky / solves
  * For collocation sets whose K(phi, phi) does not fit one GPU (BASELINE configs[4]: 1e5 points, M = 350 000, 980 GB float64)
  * the matrix is cut into block rows of SCASML_DIST_BLOCK feature rows, block row i owned by rank i % world and stored as a

@@ -17,6 +17,7 @@
 
 #include "common.hpp"
 #include "f64_mfma_tile.hpp"
+#include "gp_gram_da_table.hpp"
 
 namespace scasml {
 
@@ -126,28 +127,9 @@ __global__ __launch_bounds__(kEvThreads) void gp_gram_da_contract_kernel(int d, 
                 double r2 = fma(-2.0, t.v[it][jt][e], ni + nj);
                 r2 = r2 < 0.0 ? 0.0 : r2;
                 const double rt = tiv - tjv, S = si - sj;
-                double rho2 = fma(-rt, rt, r2);
-                rho2 = rho2 < 0.0 ? 0.0 : rho2;
-                const double kap = exp(-0.5 * a * r2);
                 const int nops_i = i < n_dom ? 4 : 1;
-                // the operator polynomials P(opx, opy) of gp_gram_mfma_kernel (ops: 0 = I, 1 = Lap, 2 = dt, 3 = div) and their derivatives in a
-                const double lap = a * a * rho2 - a * fd, lap_a = 2.0 * a * rho2 - fd;
-                const double aS = a * S, art = a * rt, mix = aS * lap - 2.0 * a * aS;
-                const double mix_a = S * lap + aS * lap_a - 4.0 * aS, tl_a = rt * lap + art * lap_a;
-                const double c3 = 2.0 * fd + 4.0, c2 = fd * fd + 2.0 * fd;
-                const double ll = a * a * a * a * rho2 * rho2 - c3 * a * a * a * rho2 + c2 * a * a;
-                const double ll_a = 4.0 * a * a * a * rho2 * rho2 - 3.0 * c3 * a * a * rho2 + 2.0 * c2 * a;
-                const double P[4][4] = {
-                    {1.0, lap, art, aS},
-                    {lap, ll, art * lap, mix},
-                    {-art, -art * lap, a - art * art, -art * aS},
-                    {-aS, -mix, -art * aS, a * fd - aS * aS}};
-                const double Pa[4][4] = {
-                    {0.0, lap_a, rt, S},
-                    {lap_a, ll_a, tl_a, mix_a},
-                    {-rt, -tl_a, 1.0 - 2.0 * art * rt, -2.0 * art * S},
-                    {-S, -mix_a, -2.0 * art * S, fd - 2.0 * aS * S}};
-                const double h = 0.5 * r2;
+                double kda[4][4];                // the pair's entries of K_a (gp_gram_da_table.hpp)
+                gram_da_pair(a, fd, r2, rt, S, kda);
 #pragma unroll
                 for (int ox = 0; ox < 4; ++ox) {
                     if (ox >= nops_i) continue;
@@ -157,7 +139,7 @@ __global__ __launch_bounds__(kEvThreads) void gp_gram_da_contract_kernel(int d, 
                     for (int oy = 0; oy < 4; ++oy) {
                         if (oy >= nops_j) continue;
                         const int64_t col = oy == 0 ? j : (int64_t)N + (int64_t)(oy - 1) * n_dom + j;
-                        const double ka = (Pa[ox][oy] - h * P[ox][oy]) * kap;
+                        const double ka = kda[ox][oy];
                         acc_q = fma(ai * alf[TBX + jl][oy], ka, acc_q);
                         acc_t = fma(A[row * lda + col], ka, acc_t);
                     }

@@ -726,6 +726,19 @@ class GP(object):
         L, info = self._factor_padded(self._gram_at(self._a_of(sigma)), nugget, "cholesky(evidence)")
         return None if info != 0 or bool(torch.isnan(L).any()) else L
 
+    def _inverse_and_alpha(self, L, zt):
+        """(A = K_p^-1 as an Mp x Mp device matrix, alpha = A z) from the padded factor L: what the gradients of the evidence and of the leave-one-out
+        likelihood both start from."""
+        torch = _lib.require_gpu()
+        lib = _lib.load()
+        M, Mp = self.phi_dim, L.shape[0]
+        s = _lib.stream_ptr()
+        A = torch.empty((Mp, Mp), dtype=torch.float64, device="cuda")
+        _lib.check(lib.scasml_cholesky_inverse(_lib.ptr(L), Mp, _lib.ptr(A), s), "cholesky_inverse")
+        alpha = torch.empty(M, dtype=torch.float64, device="cuda")
+        _lib.check(lib.scasml_gemv(_lib.ptr(A), M, Mp, _lib.ptr(zt), _lib.ptr(alpha), s), "gemv")
+        return A, alpha
+
     def _evidence(self, zt, sigma, nugget, return_grad):
         """(LML, (dLML/dlog sigma, dLML/dlog nugget) or None) at (sigma, nugget) for the device vector zt; None where K_p is not positive definite."""
         torch = _lib.require_gpu()
@@ -747,10 +760,7 @@ class GP(object):
         out[1] = torch.dot(y[:, 0], y[:, 0])
         if return_grad:
             a = self._a_of(sigma)
-            A = torch.empty((Mp, Mp), dtype=torch.float64, device="cuda")                          # K_p^-1
-            _lib.check(lib.scasml_cholesky_inverse(_lib.ptr(L), Mp, _lib.ptr(A), s), "cholesky_inverse")
-            alpha = torch.empty(M, dtype=torch.float64, device="cuda")
-            _lib.check(lib.scasml_gemv(_lib.ptr(A), M, Mp, _lib.ptr(zt), _lib.ptr(alpha), s), "gemv")
+            A, alpha = self._inverse_and_alpha(L, zt)
             work = torch.empty(int(lib.scasml_gp_gram_da_contract_doubles(self.N_domain, self.N_boundary)), dtype=torch.float64, device="cuda")
             _lib.check(lib.scasml_gp_gram_da_contract(self.d, a, _lib.ptr(self._xd), self.N_domain, _lib.ptr(self._xb), self.N_boundary, _lib.ptr(A), Mp,
                                                       _lib.ptr(alpha), _lib.ptr(work), s), "gp_gram_da_contract")
@@ -794,7 +804,7 @@ class GP(object):
         value, grad = res
         return (value, {"log_sigma": grad[0], "log_nugget": grad[1]}) if return_grad else value
 
-    def optimize_hyperparameters(self, z=None, which=("sigma", "nugget"), bounds=None, gtol=None, max_iter=50):
+    def optimize_hyperparameters(self, z=None, which=("sigma", "nugget"), bounds=None, gtol=None, max_iter=50, objective="lml"):
         '''Maximise log_marginal_likelihood(z; sigma, nugget) at FIXED z over the log of the parameters named in ``which`` (type-II maximum likelihood).
 
         A bounded BFGS iteration on the host in at most two variables (_maximize_bounded; every evaluation is one device value + gradient).  bounds:
@@ -806,9 +816,16 @@ class GP(object):
         the solvers see the new model at once -- for a linear problem this is the complete refit; for the nonlinear fit alternate
         GPsolver -> optimize_hyperparameters() -> GPsolver by hand.  When it does not, the object is left as it was.
         Returns {"sigma_start", "nugget_start", "lml_start", "sigma", "nugget", "lml", "grad": {"log_sigma", "log_nugget"}, "evaluations",
-        "iterations", "converged"}: the best point found, installed or not.'''
+        "iterations", "converged"}: the best point found, installed or not.
+
+        objective="loo" maximises loo_log_predictive instead (the sum of the leave-one-out predictive log densities; INTEGRATION.md says when to
+        prefer it): the same iteration, bounds, stopping rule (on dLOO/dlog theta) and installation, and the same report with "objective": "loo" added
+        and "loo_start" / "loo" in place of "lml_start" / "lml".'''
         torch = _lib.require_gpu()
         lib = _lib.load()
+        if objective not in ("lml", "loo"):
+            raise ValueError("objective must be 'lml' or 'loo'")
+        evaluate = self._evidence if objective == "lml" else self._loo_objective
         self._evidence_ready()
         which = (which,) if isinstance(which, str) else tuple(which)
         if not which or len(set(which)) != len(which) or any(w not in ("sigma", "nugget") for w in which):
@@ -828,19 +845,22 @@ class GP(object):
         def fun(x):
             p = dict(start)
             p.update({w: float(np.exp(v)) for w, v in zip(which, x)})
-            res = self._evidence(zt, p["sigma"], p["nugget"], True)
+            res = evaluate(zt, p["sigma"], p["nugget"], True)
             if res is None:
                 return None
             return res[0], np.array([res[1][0 if w == "sigma" else 1] for w in which])
 
-        lml_start = self._evidence(zt, start["sigma"], start["nugget"], False)
+        lml_start = evaluate(zt, start["sigma"], start["nugget"], False)
         x, val, grad, evals, iters, converged = _maximize_bounded(fun, np.log([start[w] for w in which]), lo, hi, gtol, int(max_iter))
         best = dict(start)
         best.update({w: float(np.exp(v)) for w, v in zip(which, x)})
-        full = self._evidence(zt, best["sigma"], best["nugget"], True)          # both derivatives at the returned point, held parameters included
+        full = evaluate(zt, best["sigma"], best["nugget"], True)          # both derivatives at the returned point, held parameters included
         report = {"sigma_start": start["sigma"], "nugget_start": start["nugget"], "lml_start": None if lml_start is None else lml_start[0],
                   "sigma": best["sigma"], "nugget": best["nugget"], "lml": val, "grad": {"log_sigma": full[1][0], "log_nugget": full[1][1]},
                   "evaluations": evals + 2, "iterations": iters, "converged": bool(converged)}
+        if objective == "loo":
+            report = {("loo" + k[3:] if k.startswith("lml") else k): v for k, v in report.items()}
+            report["objective"] = "loo"
         if not converged:
             return report
         self.sigma, self.nugget = best["sigma"], best["nugget"]
@@ -855,6 +875,111 @@ class GP(object):
         self.right_vector = rv.cpu().numpy()[:, None]
         self._pack(rv)
         return report
+
+    # leave-one-out cross-validation (Rasmussen & Williams 5.4.2; no counterpart in models/GP.py): what the other M - 1 collocation functionals
+    # predict for each one, the sum of those predictive log densities and its gradient in (log sigma, log nugget)
+    loo_panel_rows = 0      # rows of K_a per panel of scasml_gp_loo_da; 0: the library's default.  The result does not depend on it, bit for bit
+
+    def _loo_blocks(self):
+        N, Nb = self.N_domain, self.N_boundary
+        edges = [0, N, N + Nb, 2 * N + Nb, 3 * N + Nb, 4 * N + Nb]
+        return {name: slice(lo, hi) for name, lo, hi in zip(("u_dom", "u_bdy", "lap_dom", "dt_dom", "div_dom"), edges[:-1], edges[1:])}
+
+    def _loo_state(self, zt, sigma, nugget):
+        """(A = K_p^-1, alpha = A z, the diagonal of A over the M features) at (sigma, nugget); None where K_p is not positive definite."""
+        L = self._evidence_factor(sigma, nugget)
+        if L is None:
+            return None
+        A, alpha = self._inverse_and_alpha(L, zt)
+        diag = A.diagonal()[:self.phi_dim].clone()
+        if not bool((diag > 0.0).all()):              # also catches NaN
+            return None
+        return A, alpha, diag
+
+    def _loo_objective(self, zt, sigma, nugget, return_grad):
+        """(LOO, (dLOO/dlog sigma, dLOO/dlog nugget) or None) at (sigma, nugget) for the device vector zt; None where K_p is not positive definite.
+        The signature of _evidence, so that optimize_hyperparameters feeds either to the same iteration."""
+        torch = _lib.require_gpu()
+        lib = _lib.load()
+        state = self._loo_state(zt, sigma, nugget)
+        if state is None:
+            return None
+        A, alpha, diag = state
+        M, Mp = self.phi_dim, A.shape[0]
+        s = _lib.stream_ptr()
+        out = torch.zeros(3, dtype=torch.float64, device="cuda")      # [LOO, dLOO/da, dLOO/dnugget]
+        out[0] = (0.5 * torch.log(diag) - alpha * alpha / (2.0 * diag) - 0.5 * float(np.log(2.0 * np.pi))).sum()
+        if return_grad:
+            a = self._a_of(sigma)
+            q, v, Av, Aalpha = (torch.empty(M, dtype=torch.float64, device="cuda") for _ in range(4))
+            work = torch.empty(int(lib.scasml_gp_loo_da_doubles(self.N_domain, self.N_boundary, int(self.loo_panel_rows))), dtype=torch.float64,
+                               device="cuda")
+            _lib.check(lib.scasml_gp_loo_da(self.d, a, _lib.ptr(self._xd), self.N_domain, _lib.ptr(self._xb), self.N_boundary, _lib.ptr(A), Mp,
+                                            _lib.ptr(alpha), int(self.loo_panel_rows), _lib.ptr(q), _lib.ptr(v), _lib.ptr(work), s), "gp_loo_da")
+            _lib.check(lib.scasml_gemv(_lib.ptr(A), M, Mp, _lib.ptr(v), _lib.ptr(Av), s), "gemv")              # (Z alpha) for theta = a
+            _lib.check(lib.scasml_gemv(_lib.ptr(A), M, Mp, _lib.ptr(alpha), _lib.ptr(Aalpha), s), "gemv")      # (Z alpha) for theta = nugget
+            ssq = torch.linalg.vector_norm(A[:M, :M], dim=1).square()      # s_i = sum_j A_ij^2: a row reduction of the view, no Mp^2 temporary
+            w = 0.5 * (1.0 + alpha * alpha / diag)
+            out[1] = ((alpha * Av - w * q) / diag).sum()
+            out[2] = ((alpha * Aalpha - w * ssq) / diag).sum()
+        value, d_a, d_eta = out.cpu().numpy().tolist()
+        if not return_grad:
+            return value, None
+        return value, (-2.0 * a * d_a, float(nugget) * d_eta)
+
+    def _loo_arguments(self, sigma, nugget):
+        self._evidence_ready()
+        sigma = self.sigma if sigma is None else float(sigma)
+        nugget = self.nugget if nugget is None else float(nugget)
+        if not (sigma > 0.0 and nugget > 0.0):
+            raise ValueError("sigma and nugget must be positive")
+        return sigma, nugget
+
+    def loo(self, z=None, sigma=None, nugget=None):
+        '''Leave-one-out diagnostics of the M = 4 N_domain + N_boundary collocation functionals (compat=None only, as log_marginal_likelihood): for
+        each feature i, what the other M - 1 predict for it under K_p = K(a) + nugget I.  With A = K_p^-1 and alpha = A z
+
+            mean_i = z_i - alpha_i / A_ii,   variance_i = 1 / A_ii,   residual_i = alpha_i / sqrt(A_ii) = (z_i - mean_i) / sqrt(variance_i),
+            log_predictive_i = 1/2 log A_ii - alpha_i^2 / (2 A_ii) - 1/2 log(2 pi).
+
+        Returns {"mean", "variance", "residual", "log_predictive": float64 NumPy arrays of M in the Gram's order [u(dom), u(bdy), Lap(dom), dt(dom),
+        div(dom)], "blocks": {"u_dom", "u_bdy", "lap_dom", "dt_dom", "div_dom": the slice of each block}}.  z, sigma and nugget as in
+        log_marginal_likelihood: overrides leave the object and its cached factor alone.  Cost: the factor (cached at the object's own values),
+        scasml_cholesky_inverse, one scasml_gemv and element-wise work on M-vectors.'''
+        torch = _lib.require_gpu()
+        sigma, nugget = self._loo_arguments(sigma, nugget)
+        zt = self._evidence_z(z)
+        state = self._loo_state(zt, sigma, nugget)
+        if state is None:
+            raise ValueError("K(sigma = %g) + %g I is not positive definite in float64" % (sigma, nugget))
+        _, alpha, diag = state
+        res = {"mean": zt - alpha / diag, "variance": 1.0 / diag, "residual": alpha / torch.sqrt(diag),
+               "log_predictive": 0.5 * torch.log(diag) - alpha * alpha / (2.0 * diag) - 0.5 * float(np.log(2.0 * np.pi))}
+        res = {k: v.cpu().numpy() for k, v in res.items()}
+        res["blocks"] = self._loo_blocks()
+        return res
+
+    def loo_log_predictive(self, z=None, return_grad=False, sigma=None, nugget=None):
+        '''LOO = sum_i log p(z_i | z_-i, sigma, nugget), the leave-one-out predictive log-likelihood (the sum of loo()["log_predictive"]): the
+        model-selection criterion that trusts the prior less than the evidence does.  Same arguments, defaults and refusals as
+        log_marginal_likelihood; ValueError where K_p is not positive definite.
+
+        Returns a float; with return_grad=True ``(value, {"log_sigma": dLOO/dlog sigma, "log_nugget": dLOO/dlog nugget})``, where for theta in
+        (a, nugget), Z = A dK_p/dtheta,
+
+            dLOO/dtheta = sum_i [ alpha_i (Z alpha)_i - 1/2 (1 + alpha_i^2 / A_ii) (Z A)_ii ] / A_ii,
+            theta = a:       (Z alpha)_i = (A K_a alpha)_i,  (Z A)_ii = sum_jk A_ij K_a[j][k] A_ik;      dLOO/dlog sigma = -2 a dLOO/da
+            theta = nugget:  (Z alpha)_i = (A alpha)_i,      (Z A)_ii = sum_j A_ij^2;                    dLOO/dlog nugget = nugget dLOO/dnugget.
+
+        Cost of the gradient beyond loo(): scasml_gp_loo_da (the M^3 product A K_a A's diagonal on the FP64 matrix cores, K_a walked in row panels
+        and never stored whole; workspace (panel rows + M / 64) M doubles), two scasml_gemv and a row reduction of A.  Every sum has a fixed order:
+        two calls return the same bits.'''
+        sigma, nugget = self._loo_arguments(sigma, nugget)
+        res = self._loo_objective(self._evidence_z(z), sigma, nugget, bool(return_grad))
+        if res is None:
+            raise ValueError("K(sigma = %g) + %g I is not positive definite in float64" % (sigma, nugget))
+        value, grad = res
+        return (value, {"log_sigma": grad[0], "log_nugget": grad[1]}) if return_grad else value
 
     # joint posterior (no counterpart in models/GP.py): covariance between evaluation points and draws from N(mean, cov)
     def _cross_rows(self, x_dom, x_bdy, op, xi, out, ld, r16):
