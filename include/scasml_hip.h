@@ -226,7 +226,8 @@ int scasml_picard_tree_stderr_uz(const scasml_problem *prob_h, const scasml_plan
  *   n + 2 entries, count_h n + 1; either may be NULL.  n = 0 gives 0 and writes nothing.  < 0 on error.
  *
  * scasml_picard_tree_summands: scasml_picard_tree plus the table.  out_uz and out_uhat are bit for bit those of scasml_picard_tree with the
- *   same arguments -- at world > 1 the un-clipped partial sums.
+ *   same arguments -- at world > 1 the un-clipped partial sums.  (NaNs included: every tree entry stores a NaN of out_uz as the one pattern
+ *   0x7FC00000, since the sign an operation gives a NaN is the compiler's choice and differed between two kernels of one walk.)
  *   mode  : SCASML_MODE_MLP or SCASML_MODE_ACCUMULATE.
  *   ncol  : 1 -- the summands of u -- or 1 + d -- those of (u, z_1 .. z_d).
  *   out_y : S x ldy x ncol floats, summand-major: entry (j, root, c) at out_y[(j * ldy + root) * ncol + c]; ldy >= B, 0 means B.  A chunk of

@@ -49,6 +49,11 @@ __device__ __forceinline__ float4 f4_scale(float4 a, float s) { return make_floa
 __device__ __forceinline__ float4 mul4(float4 a, float4 b) { return make_float4(a.x * b.x, a.y * b.y, a.z * b.z, a.w * b.w); }
 __device__ __forceinline__ float clip1(float v, float c) { return v < -c ? -c : (v > c ? c : v); }  // keeps NaN (jnp.clip)
 __device__ __forceinline__ float4 clip4(float4 v, float c) { return make_float4(clip1(v.x, c), clip1(v.y, c), clip1(v.z, c), clip1(v.w, c)); }
+// A NaN leaves through out_uz as ONE bit pattern.  Which sign a NaN carries that an operation produced or passed on is the compiler's choice (a
+// negation folded into an operand flips it), so two kernels that run the same arithmetic may disagree on it, and the entries promise each other's
+// out_uz bit for bit: picard_sum_kernel<0, ACCUMULATE, 5, cubic> returned +NaN in the z of a NaN root where picard_tree_kernel returns -NaN.
+__device__ __forceinline__ float one_nan(float v) { return v != v ? __builtin_nanf("") : v; }
+__device__ __forceinline__ float4 one_nan4(float4 v) { return make_float4(one_nan(v.x), one_nan(v.y), one_nan(v.z), one_nan(v.w)); }
 // A lane holds spatial dims dim0 .. dim0 + 3 of every d-vector: 1 on those below d (live), 0 on padding
 __device__ __forceinline__ float4 live_mask(int dim0, int d) {
     return make_float4(dim0 + 0 < d ? 1.0f : 0.0f, dim0 + 1 < d ? 1.0f : 0.0f, dim0 + 2 < d ? 1.0f : 0.0f, dim0 + 3 < d ? 1.0f : 0.0f);
@@ -779,14 +784,14 @@ __global__ __launch_bounds__(256) void picard_tree_kernel(const TreeArgs a) {
         if (valid) {
             float *out = a.out_uz + local * (a.d + 1);
             if (w.gl == 0) {
-                out[0] = u;
+                out[0] = one_nan(u);
                 if constexpr (MODE == SCASML_MODE_ACCUMULATE) {
                     if (a.out_uhat) a.out_uhat[local] = w.gp_at((uint32_t)(a.ppr - 1)).x;
                 }
                 // Var <= 0 (rounding) gives 0; a NaN Var -- the root's u is NaN -- stays NaN (fmaxf would turn it into an exact-looking 0)
                 if constexpr (SE) a.out_se[local] = w.se.var <= 0.0f ? 0.0f : sqrtf(w.se.var);
             }
-            store_z(out, dim0, a.d, z);
+            store_z(out, dim0, a.d, one_nan4(z));
         }
     }
 }
@@ -837,13 +842,13 @@ __global__ __launch_bounds__(256) void picard_se_uz_kernel(const TreeArgs a) {
         float *out = a.out_uz + local * (a.d + 1);
         float *se = a.out_se + local * (a.d + 1);            // (se_u, se_z_1 .. se_z_d), the layout of the out_uz row
         if (w.gl == 0) {
-            out[0] = u;
+            out[0] = one_nan(u);
             if constexpr (MODE == SCASML_MODE_ACCUMULATE) {
                 if (a.out_uhat) a.out_uhat[local] = w.gp_at((uint32_t)(a.ppr - 1)).x;
             }
             se[0] = w.se.var <= 0.0f ? 0.0f : sqrtf(w.se.var);   // as picard_tree_kernel: Var <= 0 gives 0, a NaN Var stays NaN
         }
-        store_z(out, dim0, a.d, z);
+        store_z(out, dim0, a.d, one_nan4(z));
         const float4 v = w.sez.var;                          // this lane's live dims; padding dims (which may hold 0 * inf) are not stored
         store_z(se, dim0, a.d, make_float4(v.x <= 0.0f ? 0.0f : sqrtf(v.x), v.y <= 0.0f ? 0.0f : sqrtf(v.y),
                                            v.z <= 0.0f ? 0.0f : sqrtf(v.z), v.w <= 0.0f ? 0.0f : sqrtf(v.w)));
@@ -893,12 +898,12 @@ __global__ __launch_bounds__(256) void picard_sum_kernel(const TreeArgs a, const
     if (valid) {
         float *out = a.out_uz + local * (a.d + 1);
         if (w.gl == 0) {
-            out[0] = u;
+            out[0] = one_nan(u);
             if constexpr (MODE == SCASML_MODE_ACCUMULATE) {
                 if (a.out_uhat) a.out_uhat[local] = w.gp_at((uint32_t)(a.ppr - 1)).x;
             }
         }
-        store_z(out, dim0, a.d, z);
+        store_z(out, dim0, a.d, one_nan4(z));
     }
 }
 
