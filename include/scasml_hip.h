@@ -60,6 +60,8 @@ typedef struct {
  * Stream ids: the solvers count their calls from 0 (one id per uz_solve); SCASML_STREAM_GP_SAMPLE is reserved for scasml_gp_sample, where
  * root = sample index, site = 0 and quad q holds the normals of points 4q .. 4q+3 -- a solver would need 1.2e9 calls to reach it. */
 #define SCASML_STREAM_GP_SAMPLE 0x47505053u   /* "GPPS" */
+#define SCASML_STREAM_GP_RFF 0x47505246u      /* "GPRF": the Fourier features of scasml_gp_rff_functionals */
+#define SCASML_STREAM_GP_RFF_NOISE 0x4750524Eu /* "GPRN": the observation noise of scasml_gp_rff_noise */
 typedef struct {
     uint64_t seed;
     uint32_t stream;  /* advanced by the host once per solver call (replaces MLP.py:220 key splitting) */
@@ -603,6 +605,27 @@ int scasml_gp_variance(const double *L, int64_t Mp, double *rows, int64_t ld, in
  * S = 0 does nothing. */
 int scasml_gp_sample(const double *Lc, int64_t np, int64_t n, const double *mean, uint64_t seed, int64_t sample0, int64_t S, double *out,
                      int64_t ld_out, void *stream);
+
+/* Added within ABI 7 (additive).  The prior term of a pathwise posterior draw (Matheron's rule): random Fourier features of
+ * kappa(x, y) = exp(-a |x - y|^2 / 2), whose spectral measure is omega ~ N(0, a I_{d+1}), and the four collocation functionals of the draw, float64:
+ *   theta_f = omega_f . x_i (time last)     P_f = wc_f cos theta_f + ws_f sin theta_f     Q_f = ws_f cos theta_f - wc_f sin theta_f
+ *   out[(s*n + i)*4 + 0] = u   = F^-1/2 sum_f P_f                       out[.. + 1] = Lap = F^-1/2 sum_f -|omega_f,x|^2 P_f   (spatial components)
+ *   out[(s*n + i)*4 + 2] = dt  = F^-1/2 sum_f omega_f,t Q_f             out[.. + 3] = div = F^-1/2 sum_f (sum_k omega_f,k) Q_f   (spatial k)
+ * for the n points x (rows of d+1 float32 coordinates, row stride ld_x floats) and the draws sample0 .. sample0 + S.  Every draw has its own F
+ * features: with v = normal4(quad, site = f, root = sample0 + s, stream = SCASML_STREAM_GP_RFF, key = seed) over the quads of d + 3 normals -- on the
+ * host oracle.philox.normals(seed, SCASML_STREAM_GP_RFF, [r], f, d + 3)[0] -- omega_f = sqrt(a) * (double)v[0 : d+1] (the float32 normal widened, then
+ * multiplied in double), wc_f = v[d+1], ws_f = v[d+2].  E[L_x f . L_y f] = L_x L_y kappa exactly, for every operator pair and every F; only the
+ * Gaussianity of the joint is asymptotic in F.
+ * One workgroup owns one draw and 64 points and sweeps the features 64 at a time: theta on v_mfma_f64_16x16x4_f64 (K = d + 1), the omega stage generated
+ * from Philox in registers (never in HBM), sincos in double, one fixed summation order, no atomics (csrc/gp_rff.hip).  A point's four values are a
+ * function of (x_i, d, a, F, seed, sample0 + s) alone, bit for bit: not of n, ld_x, the point's position, S or the split of draws over calls.
+ * Null pointers, d < 1 or d > SCASML_MAX_DIM, a not positive, F < 1, ld_x < d + 1, negative n, S or sample0: SCASML_ERR_ARG; a draw index >= 2^32:
+ * SCASML_ERR_UNSUPPORTED; n = 0 or S = 0 does nothing.
+ * scasml_gp_rff_noise: out[s*ld + j] = component j % 4 of normal4(quad = j / 4, site = 0, root = sample0 + s, stream = SCASML_STREAM_GP_RFF_NOISE,
+ * key = seed) widened to double, j < M <= ld -- oracle.philox.normals(seed, SCASML_STREAM_GP_RFF_NOISE, [r], 0, M)[0].  The same refusals. */
+int scasml_gp_rff_functionals(int32_t d, double a, const float *x, int64_t n, int64_t ld_x, int32_t F, uint64_t seed, int64_t sample0, int64_t S,
+                              double *out, void *stream);
+int scasml_gp_rff_noise(int64_t M, uint64_t seed, int64_t sample0, int64_t S, double *out, int64_t ld, void *stream);
 
 /* Added within ABI 7 (additive).  The device pieces of the GP log marginal likelihood and its gradient (csrc/gp_evidence.hip), float64:
  *   LML = -1/2 z^T alpha - 1/2 log det K_p - M/2 log(2 pi),   K_p = K(a) + nugget I,  alpha = K_p^-1 z,  a = 1 / sigma^2

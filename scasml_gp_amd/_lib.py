@@ -21,6 +21,8 @@ EQ_QUADRATIC_GRADIENT_REACTION_DIFFUSION = 2      # f(u, sum z, |z|^2): surrogat
 # round16 bits of the as-coded GP entry points (include/scasml_hip.h); bit 2 means one thing for the Gram, Gram rows, cross rows and
 # float64 evaluation, another for the matrix-core evaluation
 STREAM_GP_SAMPLE = 0x47505053   # Philox stream id of scasml_gp_sample (SCASML_STREAM_GP_SAMPLE); the solvers count theirs from 0
+STREAM_GP_RFF = 0x47505246      # ... of scasml_gp_rff_functionals' Fourier features (SCASML_STREAM_GP_RFF)
+STREAM_GP_RFF_NOISE = 0x4750524E   # ... of scasml_gp_rff_noise (SCASML_STREAM_GP_RFF_NOISE)
 ROUND16_ENTRIES = 1       # every kernel entry rounded to float16
 ROUND16_OUTPUTS = 2       # evaluation: u_hat and eps_PDE leave as float16 values
 ROUND16_F16_OPS = 4       # Gram, Gram rows, cross rows, float64 evaluation: the float16 op sequence on float16 rows
@@ -129,6 +131,9 @@ SIGNATURES = {
                                        C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p]),
     "scasml_gp_variance": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_int64, C.c_double, C.c_void_p, C.c_void_p]),
     "scasml_gp_sample": (C.c_int, [C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_uint64, C.c_int64, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p]),
+    "scasml_gp_rff_functionals": (C.c_int, [C.c_int32, C.c_double, C.c_void_p, C.c_int64, C.c_int64, C.c_int32, C.c_uint64, C.c_int64, C.c_int64, C.c_void_p,
+                                            C.c_void_p]),
+    "scasml_gp_rff_noise": (C.c_int, [C.c_int64, C.c_uint64, C.c_int64, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p]),
     "scasml_chol_logdet": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]),
     "scasml_gp_gram_da_contract_doubles": (C.c_int64, [C.c_int32, C.c_int32]),
     "scasml_gp_gram_da_contract": (C.c_int, [C.c_int32, C.c_double, C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.c_int64, C.c_void_p,

@@ -12,6 +12,8 @@ What runs where:
 * predict / compute_gradient / compute_PDE_loss (:653-687, 746-769) .. scasml_gp_eval, scasml_gp_gradient
 * log marginal likelihood, its gradient in (log sigma, log nugget) and a fit of the two (no counterpart: :25-26 hard-code them; compat=None only)
   .............................................................. scasml_chol_logdet, scasml_gp_gram_da_contract
+* posterior draws as functions (no counterpart; compat=None only): GP.sample_functions -> GPFunctionDraws ... scasml_gp_rff_functionals,
+  scasml_gp_rff_noise, scasml_trsm_lower, scasml_gp_cross_rows, scasml_gemm_nt_sub
 
 Two surrogates (``compat``):
 * ``None``: the operators the reference documents -- exact Laplacian features, no float16 rounding.
@@ -114,6 +116,66 @@ def _maximize_bounded(fun, x0, lo, hi, gtol, max_iter):
             V = np.eye(len(x)) - rho * np.outer(s, y)
             H = V @ H @ V.T + rho * np.outer(s, s)
         x, f, g = xn, fn, gn
+
+
+class GPFunctionDraws(object):
+    """Posterior draws of a GP as FUNCTIONS (GP.sample_functions; pathwise conditioning, Wilson et al. 2020): draw s is
+        post_s(x) = f_s(x) + k(x, phi)^T right_vectors[s],     (L post_s)(x) = (L f_s)(x) + (L_x k)(x, phi)^T right_vectors[s],   L in {I, Lap, dt, div}
+    with f_s the random-Fourier-feature prior draw of scasml_gp_rff_functionals.  The object holds the (S, M) right vectors and the five scalars that
+    name the prior draws (d, a, n_features, seed, sample0) -- not the features, which the kernel regenerates from Philox at every evaluation -- and the
+    GP whose collocation points the cross rows are taken against.  Draw s is a function of (model, seed, sample0 + s, n_features) alone: the points may
+    be split, permuted or revisited freely and every value comes back bit for bit."""
+
+    def __init__(self, gp, right_vectors, n_features, seed, sample0):
+        torch = _lib.require_gpu()
+        self.gp, self.right_vectors = gp, right_vectors
+        self.d, self.a, self.n_features, self.seed, self.sample0 = gp.d, gp.a, int(n_features), int(seed), int(sample0)
+        S, M = right_vectors.shape
+        # -right_vectors in rows of Mp columns, the padding zero: what scasml_gemm_nt_sub takes (C -= rows B^T adds the data term)
+        self._neg = torch.zeros((S, _round_up(max(M, 1), 32)), dtype=torch.float64, device="cuda")
+        self._neg[:, :M] = -right_vectors
+
+    @property
+    def n_samples(self):
+        return self.right_vectors.shape[0]
+
+    def _evaluate(self, x, ops):
+        """(S, n, len(ops)) float64 on the device, and whether x was a NumPy array."""
+        torch = _lib.require_gpu()
+        lib = _lib.load()
+        gp = self.gp
+        xi, was_numpy, _ = gp._rows_device(x)
+        S, n, Mp = self.n_samples, xi.shape[0], self._neg.shape[1]
+        out = torch.empty((S, n, len(ops)), dtype=torch.float64, device="cuda")
+        if S == 0 or n == 0:
+            return out, was_numpy
+        s = _lib.stream_ptr()
+        chunk = int(max(1, min(gp.variance_buffer_bytes // (8 * Mp), gp.cross_rows_per_call, n)))
+        rows = torch.zeros((chunk, Mp), dtype=torch.float64, device="cuda")      # columns M .. Mp stay zero: the cross rows fill 0 .. M
+        for lo in range(0, n, chunk):
+            xc = xi[lo:lo + chunk]
+            c = xc.shape[0]
+            prior = gp._rff_functionals(xc, self.n_features, self.seed, self.sample0, S)       # (S, c, 4)
+            vals = prior[:, :, list(ops)].permute(1, 2, 0).contiguous()                        # (c, ops, S): one (c x S) block per operator
+            for k, op in enumerate(ops):
+                gp._cross_rows(gp._xd, gp._xb, op, xc, rows, Mp, 0)
+                block = vals[:, k, :]
+                _lib.check(lib.scasml_gemm_nt_sub(_lib.ptr(block), vals.stride(0), c, S, _lib.ptr(rows), Mp, _lib.ptr(self._neg), Mp, Mp, 0, 0, 0, s),
+                           "gemm_nt_sub")
+            out[:, lo:lo + c, :] = vals.permute(2, 0, 1)
+        return out, was_numpy
+
+    def predict(self, x):
+        """(S, n) float64: every draw at the points x (NumPy in, NumPy out; CUDA tensor in, CUDA tensor out).  The mean part is the float64 statement
+        k(x)^T right_vector, not the bf16 evaluation of GP.predict."""
+        out, was_numpy = self._evaluate(x, (0,))
+        out = out[:, :, 0].contiguous()
+        return out.cpu().numpy() if was_numpy else out
+
+    def functionals(self, x):
+        """(S, n, 4) float64: u, Lap u, dt u and div u (= sum_k d_k u, as everywhere in this library) of every draw at the points x."""
+        out, was_numpy = self._evaluate(x, (0, 1, 2, 3))
+        return out.cpu().numpy() if was_numpy else out
 
 
 class GP(object):
@@ -1133,6 +1195,63 @@ class GP(object):
             _lib.check(lib.scasml_gp_sample(_lib.ptr(Lc), npad, n, _lib.ptr(mean), seed, sample0 + lo, c, _lib.ptr(dev), n, s), "gp_sample")
             out[lo:lo + c] = dev[:c].cpu().numpy()
         return out
+
+    # pathwise posterior draws (no counterpart in models/GP.py): functions, not vectors -- a random-Fourier-feature prior draw plus the data term
+    def _rff_functionals(self, xi, n_features, seed, sample0, S):
+        """(S, n, 4) float64 device tensor: u, Lap, dt, div of the prior draws sample0 .. sample0 + S at the float32 device rows xi."""
+        torch = _lib.require_gpu()
+        out = torch.empty((S, xi.shape[0], 4), dtype=torch.float64, device="cuda")
+        if out.numel():
+            _lib.check(_lib.load().scasml_gp_rff_functionals(self.d, self.a, _lib.ptr(xi), xi.shape[0], xi.stride(0), int(n_features),
+                                                             int(seed) & 0xFFFFFFFFFFFFFFFF, int(sample0), S, _lib.ptr(out), _lib.stream_ptr()),
+                       "gp_rff_functionals")
+        return out
+
+    def sample_functions(self, n_samples, seed=0, n_features=2048, sample0=0, z=None):
+        '''n_samples posterior draws as functions (GPFunctionDraws: .right_vectors, .predict(x), .functionals(x)), by pathwise conditioning
+        (Matheron's rule; Wilson et al., ICML 2020):
+            post_s(x) = f_s(x) + k(x, phi)^T K_p^-1 (z - Phi[f_s] - sqrt(nugget) eps_s)
+        f_s is a prior draw from n_features random Fourier features of its own (scasml_gp_rff_functionals, csrc/gp_rff.hip), Phi[f_s] its collocation
+        functionals in the Gram's order [u(dom), u(bdy), Lap(dom), dt(dom), div(dom)], eps_s ~ N(0, I) (scasml_gp_rff_noise) and z the feature
+        values (default: those of log_marginal_likelihood -- b(sol) of the fit, else K_p right_vector).  The S right-hand sides are solved with the cached factor
+        (two scasml_trsm_lower calls, nrhs = S).  Mean and covariance of the draws are exactly k K_p^-1 z and predict_covariance for every
+        n_features; only the Gaussianity of the joint is asymptotic in it.  The mean part is the float64 statement k(x)^T right_vector, not the bf16
+        evaluation of GP.predict.  Unlike sample_posterior nothing n x n is factored: the cost is linear in the points, a draw can be evaluated
+        anywhere, again, and differentiated (Lap, dt, div, and so its PDE residual).  Draw s is a function of (model, seed, sample0 + s, n_features)
+        alone.  compat=None only.'''
+        torch = _lib.require_gpu()
+        lib = _lib.load()
+        if self.compat == "reference":
+            raise ValueError("pathwise draws need compat=None: the as-coded matrix is not the Gram of one kernel and has no spectral density")
+        if getattr(self, "_xd", None) is None:
+            raise _lib.ScasmlError("no collocation points yet: call GPsolver / kernel_phi_phi / load_right_vector first")
+        S, F, sample0 = int(n_samples), int(n_features), int(sample0)
+        if S < 0 or sample0 < 0:
+            raise ValueError("n_samples and sample0 must not be negative")
+        if F < 1 or F >= 1 << 31:
+            raise ValueError("n_features must lie in 1 .. 2^31 - 1, got %d" % F)
+        if sample0 + S > 1 << 32:
+            raise ValueError("draw indices %d .. %d reach 2^32 (the Philox root word is 32 bits)" % (sample0, sample0 + S - 1))
+        zt = self._evidence_z(z)
+        L = self._variance_factor()
+        N, Nb, M, Mp = self.N_domain, self.N_boundary, self.phi_dim, L.shape[0]
+        s = _lib.stream_ptr()
+        seed = int(seed) & 0xFFFFFFFFFFFFFFFF
+        rhs = torch.zeros((S, Mp), dtype=torch.float64, device="cuda")
+        if S:
+            _lib.check(lib.scasml_gp_rff_noise(M, seed, sample0, S, _lib.ptr(rhs), Mp, s), "gp_rff_noise")
+            rhs[:, :M].mul_(-float(np.sqrt(self.nugget))).add_(zt)
+            fd = self._rff_functionals(self._xd, F, seed, sample0, S)
+            rhs[:, :N] -= fd[:, :, 0]
+            if Nb:
+                rhs[:, N:N + Nb] -= self._rff_functionals(self._xb, F, seed, sample0, S)[:, :, 0]
+            for k in (1, 2, 3):
+                rhs[:, k * N + Nb:(k + 1) * N + Nb] -= fd[:, :, k]
+            B = rhs.t().contiguous()                                   # (Mp, S): the right-hand sides as columns
+            for trans in (0, 1):
+                _lib.check(lib.scasml_trsm_lower(_lib.ptr(L), Mp, _lib.ptr(B), S, trans, s), "trsm_lower")
+            rhs = B.t()
+        return GPFunctionDraws(self, rhs[:, :M].contiguous(), F, seed, sample0)
 
     def compute_gradient(self, x_t_infer, sol_infer=None):
         '''(n, d+1) gradient of the posterior mean, time derivative last (models/GP.py:673-687).'''
