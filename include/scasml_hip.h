@@ -652,7 +652,7 @@ int scasml_gp_gram_da_contract(int32_t d, double a, const float *x_dom, int32_t 
 /* LOO: added within ABI 7 (additive).  Feature rows [row0, row0 + nrows) x columns [0, ncols) of K_a = dK/da into out (row-major, leading dimension
  * ld >= ncols): the twin of scasml_gp_gram_rows -- the same arguments, block order [u(dom), u(bdy), Lap(dom), dt(dom), div(dom)], 64 x 64 FP64-MFMA pair
  * tile and refusals -- with the entries (P_a - r^2 P / 2) kappa that scasml_gp_gram_da_contract contracts (one statement of the table serves both,
- * csrc/gp_gram_da_table.hpp).  An entry is a function of its pair of points alone, bit for bit: it does not depend on row0, nrows or ncols.
+ * csrc/gp_gram_table.hpp).  An entry is a function of its pair of points alone, bit for bit: it does not depend on row0, nrows or ncols.
  * More than 65535 point tiles of 64, or row tiles per call: SCASML_ERR_UNSUPPORTED, before anything is launched. */
 int scasml_gp_gram_da_rows(int32_t d, double a, const float *x_dom, int32_t n_dom, const float *x_bdy, int32_t n_bdy, int64_t row0, int32_t nrows,
                            int64_t ncols, double *out, int64_t ld, void *stream);

@@ -600,29 +600,14 @@ extern "C" int scasml_gp_gram_compat_rows(int32_t d, double a, const float *x_do
     if (int rc = check_idx(idx_h, d, ix, "gp_gram_compat_rows")) return rc;
     if (nrows == 0 || ncols == 0) return 0;
     const int N = n_dom + n_bdy;
-    int64_t r = row0;
-    const int64_t r_end = row0 + nrows;
-    while (r < r_end) {                         // one launch per operator segment of the row range (as scasml_gp_gram_rows)
-        int ox, i_lo;
-        int64_t seg_end;
-        if (r < N) {
-            ox = 0;
-            i_lo = (int)r;
-            seg_end = N;
-        } else {
-            const int64_t q = r - N;
-            ox = 1 + (int)(q / n_dom);
-            i_lo = (int)(q % n_dom);
-            seg_end = (int64_t)N + (int64_t)ox * n_dom;
-        }
-        const int64_t stop = seg_end < r_end ? seg_end : r_end;
-        const int n_i = (int)(stop - r);
+    const int rc = for_each_operator_segment(n_dom, n_bdy, row0, nrows, [&](int ox, int i_lo, int n_i, int64_t row_offset) {   // one launch per piece
         const unsigned gy = (unsigned)((n_i + 15) / 16);
         if (gy > 65535) return fail(SCASML_ERR_UNSUPPORTED, "gp_gram_compat_rows: too many rows per call");
         hipLaunchKernelGGL(gp_gram_compat_rows_kernel, dim3((N + 15) / 16, gy), dim3(16, 16), 0, (hipStream_t)stream, d, a, x_dom, n_dom, x_bdy, n_bdy,
-                           ix, round16, ox, i_lo, n_i, ncols, out + (r - row0) * ld, ld);
-        r = stop;
-    }
+                           ix, round16, ox, i_lo, n_i, ncols, out + row_offset * ld, ld);
+        return 0;
+    });
+    if (rc) return rc;
     return check_launch("gp_gram_compat_rows launch");
 }
 

@@ -3,9 +3,9 @@
 // (1) scasml_chol_logdet: 2 sum_i log L[i][i] of the factor scasml_cholesky leaves (its identity padding adds log 1 = 0).
 // (2) scasml_gp_gram_da_contract: sum_ij alpha_i alpha_j K_a[i][j] and sum_ij A[i][j] K_a[i][j] in ONE pass of Gram-tile size, K_a never stored.
 //
-// The pass is gp_gram_mfma_kernel's 64 x 64 pair tile (gp_train.hip): x.y on v_mfma_f64_16x16x4_f64, K = d + 1 streamed through LDS, per-point
+// The pass is the Gram's 64 x 64 pair tile (gp_gram_tile.hpp): x.y on v_mfma_f64_16x16x4_f64, K = d + 1 streamed through LDS, per-point
 // statistics in LDS.  An entry of K is P(ox, oy) kappa with kappa = exp(-a r^2 / 2), so the entry of K_a is (P_a - r^2 P / 2) kappa, P_a = dP/da at
-// fixed geometry.  The epilogue evaluates that table for the pair's up to 16 entries and multiplies each by its A entry and its alpha_i alpha_j (the
+// fixed geometry (gp_gram_table.hpp).  The visit evaluates that table for the pair's up to 16 entries and multiplies each by its A entry and its alpha_i alpha_j (the
 // alphas of the tile's 64 + 64 points sit in LDS beside the statistics).  K_a is symmetric and A is read as a full symmetric matrix (what
 // scasml_cholesky_inverse leaves), so only the tiles on or below the diagonal are walked and the off-diagonal ones count twice.
 //
@@ -16,8 +16,7 @@
 #include <math.h>
 
 #include "common.hpp"
-#include "f64_mfma_tile.hpp"
-#include "gp_gram_da_table.hpp"
+#include "gp_gram_tile.hpp"
 
 namespace scasml {
 
@@ -52,100 +51,43 @@ __device__ __forceinline__ void ev_tile_of_block(int64_t b, int &ti, int &tj) {
     tj = (int)(b - r * (r + 1) / 2);
 }
 
-__global__ __launch_bounds__(kEvThreads) void gp_gram_da_contract_kernel(int d, double a, const float *x_dom, int n_dom, const float *x_bdy, int n_bdy,
-                                                                         const double *__restrict__ A, int64_t lda, const double *__restrict__ alpha,
-                                                                         double *partials) {
-    constexpr int NT = 2, TBX = 32 * NT, PER = TBX * NB / kEvThreads;
+__global__ __launch_bounds__(kGramThreads) void gp_gram_da_contract_kernel(GramPoints pts, double a, const double *__restrict__ A, int64_t lda,
+                                                                           const double *__restrict__ alpha, double *partials) {
     extern __shared__ __attribute__((aligned(16))) double smem[];
-    __shared__ double stat[2 * TBX][4];          // (|x|^2 with t, sum of the spatial coordinates, t) of the tile's 64 + 64 points
-    __shared__ double alf[2 * TBX][4];           // alpha at the point's u, Lap, dt, div features (0 where a boundary point has none)
-    __shared__ double wsum[kEvThreads / 64][2];
-    const int N = n_dom + n_bdy;
+    __shared__ double stat[2 * kGramTile][4];
+    __shared__ double alf[2 * kGramTile][4];     // alpha at the point's u, Lap, dt, div features (0 where a boundary point has none)
+    __shared__ double wsum[kGramThreads / 64][2];
     int ti, tj;
     ev_tile_of_block(blockIdx.x, ti, tj);
-    const int i0 = ti * TBX, j0 = tj * TBX;
-    auto row_of = [&](int p) { return p < n_dom ? x_dom + (int64_t)p * (d + 1) : x_bdy + (int64_t)(p - n_dom) * (d + 1); };
-    {   // two threads per point, even / odd coordinates, combined with one shuffle (gp_gram_mfma_kernel)
+    const int i0 = ti * kGramTile, j0 = tj * kGramTile;
+    {   // two threads per point as in the tile's statistics; this thread's two of the point's four alphas: operators par and par + 2
         const int q = threadIdx.x >> 1, par = threadIdx.x & 1;
-        const int p = q < TBX ? i0 + q : j0 + q - TBX;
-        double n = 0.0, sx = 0.0, tt = 0.0;
-        if (p < N) {
-            const float *x = row_of(p);
-            for (int k = par; k < d; k += 2) {
-                const double v = (double)x[k];
-                n = fma(v, v, n);
-                sx += v;
-            }
-            tt = (double)x[d];
-        }
-        n += __shfl_xor(n, 1);
-        sx += __shfl_xor(sx, 1);
-        if (par == 0) {
-            stat[q][0] = fma(tt, tt, n);
-            stat[q][1] = sx;
-            stat[q][2] = tt;
-        }
-        // this thread's two of the point's four alphas: operators par and par + 2
+        const int p = q < kGramTile ? i0 + q : j0 + q - kGramTile;
 #pragma unroll
         for (int h = 0; h < 2; ++h) {
             const int op = par + 2 * h;
-            double v = 0.0;
-            if (p < N && (op == 0 || p < n_dom)) v = alpha[op == 0 ? (int64_t)p : (int64_t)N + (int64_t)(op - 1) * n_dom + p];
-            alf[q][op] = v;
+            alf[q][op] = p < pts.N() && op < pts.nops(p) ? alpha[pts.feature(op, p)] : 0.0;
         }
-    }   // visible to everyone after the barriers of the K loop below
-    TileAcc<NT> t;
-    mfma_tile_zero(t);
-    const int64_t kend = ((int64_t)d + 1 + NB - 1) / NB * NB;
-    mfma_tile_k_loop<NT>(smem, 0, kend, [&](int64_t kk, double (&ra)[PER], double (&rb)[PER]) {
-#pragma unroll
-        for (int e = 0; e < PER; ++e) {
-            const int idx = threadIdx.x + e * kEvThreads, rr = idx / NB, cc = idx % NB;
-            const int k = (int)kk + cc;
-            ra[e] = (i0 + rr < N && k <= d) ? (double)row_of(i0 + rr)[k] : 0.0;
-            rb[e] = (j0 + rr < N && k <= d) ? (double)row_of(j0 + rr)[k] : 0.0;
-        }
-    }, [] {}, t);
-    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-    const int wr = (wv >> 1) * (16 * NT), wc = (wv & 1) * (16 * NT);
-    const int l15 = lane & 15, l4 = lane >> 4;
-    const double fd = (double)d;
+    }   // visible to everyone after the barriers of the tile's K loop
+    const double fd = (double)pts.d;
     double acc_q = 0.0, acc_t = 0.0;             // alpha^T K_a alpha and <A, K_a> over this thread's pairs
+    gram_pair_tile(pts, i0, pts.N(), j0, smem, stat, [&](int i, int j, int il, int jl, double r2, double rt, double S) {
+        double ka[4][4];
+        gram_pair<kGramKa>(a, fd, r2, rt, S, ka);
+        const int nops_i = pts.nops(i), nops_j = pts.nops(j);
 #pragma unroll
-    for (int jt = 0; jt < NT; ++jt) {
-        const int jl = wc + 16 * jt + l15, j = j0 + jl;
-        if (j >= N) continue;
-        const double nj = stat[TBX + jl][0], sj = stat[TBX + jl][1], tjv = stat[TBX + jl][2];
-        const int nops_j = j < n_dom ? 4 : 1;
+        for (int ox = 0; ox < 4; ++ox) {
+            if (ox >= nops_i) continue;
+            const double *Arow = A + pts.feature(ox, i) * lda;
 #pragma unroll
-        for (int it = 0; it < NT; ++it)
-#pragma unroll
-            for (int e = 0; e < 4; ++e) {
-                const int il = wr + 16 * it + l4 + 4 * e, i = i0 + il;
-                if (i >= N) continue;
-                const double ni = stat[il][0], si = stat[il][1], tiv = stat[il][2];
-                double r2 = fma(-2.0, t.v[it][jt][e], ni + nj);
-                r2 = r2 < 0.0 ? 0.0 : r2;
-                const double rt = tiv - tjv, S = si - sj;
-                const int nops_i = i < n_dom ? 4 : 1;
-                double kda[4][4];                // the pair's entries of K_a (gp_gram_da_table.hpp)
-                gram_da_pair(a, fd, r2, rt, S, kda);
-#pragma unroll
-                for (int ox = 0; ox < 4; ++ox) {
-                    if (ox >= nops_i) continue;
-                    const int64_t row = ox == 0 ? i : (int64_t)N + (int64_t)(ox - 1) * n_dom + i;
-                    const double ai = alf[il][ox];
-#pragma unroll
-                    for (int oy = 0; oy < 4; ++oy) {
-                        if (oy >= nops_j) continue;
-                        const int64_t col = oy == 0 ? j : (int64_t)N + (int64_t)(oy - 1) * n_dom + j;
-                        const double ka = kda[ox][oy];
-                        acc_q = fma(ai * alf[TBX + jl][oy], ka, acc_q);
-                        acc_t = fma(A[row * lda + col], ka, acc_t);
-                    }
-                }
+            for (int oy = 0; oy < 4; ++oy) {
+                if (oy >= nops_j) continue;
+                acc_q = fma(alf[il][ox] * alf[kGramTile + jl][oy], ka[ox][oy], acc_q);
+                acc_t = fma(Arow[pts.feature(oy, j)], ka[ox][oy], acc_t);
             }
-    }
+        }
+    });
+    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
 #pragma unroll
     for (int m = 32; m > 0; m >>= 1) {
         acc_q += __shfl_xor(acc_q, m);
@@ -207,11 +149,11 @@ extern "C" int scasml_gp_gram_da_contract(int32_t d, double a, const float *x_do
         return fail(SCASML_ERR_UNSUPPORTED, "gp_gram_da_contract: too many collocation points for one launch");
     const int64_t tiles = ev_tiles(n_dom, n_bdy);      // <= 65535 * 65536 / 2 < 2^31: one grid dimension
     if (hipFuncSetAttribute(reinterpret_cast<const void *>(gp_gram_da_contract_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
-                            (int)tile_lds_bytes<2>()) != hipSuccess)
+                            (int)kGramLdsBytes) != hipSuccess)
         return fail(SCASML_ERR_HIP, "gp_gram_da_contract: cannot reserve LDS");
     double *partials = out_dev + 2;
-    hipLaunchKernelGGL(gp_gram_da_contract_kernel, dim3((unsigned)tiles), dim3(kEvThreads), tile_lds_bytes<2>(), (hipStream_t)stream, d, a, x_dom, n_dom,
-                       x_bdy, n_bdy, A, lda, alpha, partials);
+    hipLaunchKernelGGL(gp_gram_da_contract_kernel, dim3((unsigned)tiles), dim3(kGramThreads), kGramLdsBytes, (hipStream_t)stream,
+                       GramPoints{d, x_dom, n_dom, x_bdy, n_bdy}, a, A, lda, alpha, partials);
     hipLaunchKernelGGL(gp_evidence_sum_kernel, dim3(1), dim3(kEvThreads), 0, (hipStream_t)stream, partials, tiles, out_dev);
     return check_launch("gp_gram_da_contract launch");
 }

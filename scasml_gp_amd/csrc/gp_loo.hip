@@ -2,8 +2,8 @@
 // With A = K_p^-1, alpha = A z and K_a = dK/da (a = 1 / sigma^2) the gradient of the LOO predictive log-likelihood needs, for every feature i,
 //   q_i = [A K_a A]_ii = sum_jk A[i][j] K_a[j][k] A[i][k]     and     v_i = [K_a alpha]_i
 // (Rasmussen & Williams 5.4.2).  q is an M^3 product with a matrix the library never stores whole:
-// (1) scasml_gp_gram_da_rows: feature rows of K_a, the twin of scasml_gp_gram_rows (gp_train.hip) -- the same 64 x 64 pair tile, x.y on
-//     v_mfma_f64_16x16x4_f64, the entries (P_a - r^2 P / 2) kappa of gp_gram_da_table.hpp in place of P kappa.
+// (1) scasml_gp_gram_da_rows: feature rows of K_a, the twin of scasml_gp_gram_rows (gp_train.hip) -- the same rows kernel of the 64 x 64 pair
+//     tile (gp_gram_tile.hpp), instantiated for the entries (P_a - r^2 P / 2) kappa of gp_gram_table.hpp in place of P kappa.
 // (2) scasml_gp_loo_da: K_a is walked in panels of panel_rows feature rows.  A panel P (panel_rows x M) is written by (1) into the workspace, v of
 //     its rows is one row reduction of it, and the tile kernel forms T = A[I, :] P^T for a block I of 64 rows of A and 64 rows c of the panel on
 //     v_mfma_f64_16x16x4_f64 (K dimension M, streamed through LDS by mfma_tile_k_loop).  K_a is symmetric, so T[i][c] = [A K_a]_i,row0+c and the
@@ -18,92 +18,13 @@
 
 #include "common.hpp"
 #include "f64_mfma_tile.hpp"
-#include "gp_gram_da_table.hpp"
+#include "gp_gram_tile.hpp"
 
 namespace scasml {
 
 constexpr int kLooThreads = 256;
 constexpr int kLooTile = 64;                 // rows of A and rows of the panel per workgroup
 constexpr int kLooDefaultPanelRows = 512;
-
-// gp_gram_rows_mfma_kernel (gp_train.hip) with the entries of K_a: the rows of one operator `ox` at the points [i_lo, i_lo + n_i) against every
-// collocation point j, columns < ncols only; out points at the first of those rows.  OX is a template argument so that the row of the table is
-// picked at compile time (indexed at run time the 4 x 4 table went to scratch memory)
-template <int OX>
-__global__ __launch_bounds__(kLooThreads) void gp_gram_da_rows_kernel(int d, double a, const float *x_dom, int n_dom, const float *x_bdy, int n_bdy,
-                                                                      int i_lo, int n_i, int64_t ncols, double *out, int64_t ld) {
-    constexpr int NT = 2, TBX = 32 * NT, PER = TBX * NB / kLooThreads;
-    extern __shared__ __attribute__((aligned(16))) double smem[];
-    __shared__ double stat[2 * TBX][4];          // (|x|^2 with t, sum of the spatial coordinates, t) of the tile's 64 + 64 points
-    const int N = n_dom + n_bdy;
-    const int i0 = i_lo + blockIdx.y * TBX, j0 = blockIdx.x * TBX, i_end = i_lo + n_i;
-    if ((int64_t)j0 >= ncols) return;            // block-uniform: every column of this tile lies beyond the asked part of these rows
-    auto row_of = [&](int p) { return p < n_dom ? x_dom + (int64_t)p * (d + 1) : x_bdy + (int64_t)(p - n_dom) * (d + 1); };
-    {   // two threads per point, even / odd coordinates, combined with one shuffle (gp_gram_mfma_kernel)
-        const int q = threadIdx.x >> 1, par = threadIdx.x & 1;
-        const int p = q < TBX ? i0 + q : j0 + q - TBX;
-        const bool live = q < TBX ? p < i_end : p < N;
-        double n = 0.0, sx = 0.0, tt = 0.0;
-        if (live) {
-            const float *x = row_of(p);
-            for (int k = par; k < d; k += 2) {
-                const double v = (double)x[k];
-                n = fma(v, v, n);
-                sx += v;
-            }
-            tt = (double)x[d];
-        }
-        n += __shfl_xor(n, 1);
-        sx += __shfl_xor(sx, 1);
-        if (par == 0) {
-            stat[q][0] = fma(tt, tt, n);
-            stat[q][1] = sx;
-            stat[q][2] = tt;
-        }
-    }   // visible to everyone after the barriers of the K loop below
-    TileAcc<NT> t;
-    mfma_tile_zero(t);
-    const int64_t kend = ((int64_t)d + 1 + NB - 1) / NB * NB;
-    mfma_tile_k_loop<NT>(smem, 0, kend, [&](int64_t kk, double (&ra)[PER], double (&rb)[PER]) {
-#pragma unroll
-        for (int e = 0; e < PER; ++e) {
-            const int idx = threadIdx.x + e * kLooThreads, rr = idx / NB, cc = idx % NB;
-            const int k = (int)kk + cc;
-            ra[e] = (i0 + rr < i_end && k <= d) ? (double)row_of(i0 + rr)[k] : 0.0;
-            rb[e] = (j0 + rr < N && k <= d) ? (double)row_of(j0 + rr)[k] : 0.0;
-        }
-    }, [] {}, t);
-    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-    const int wr = (wv >> 1) * (16 * NT), wc = (wv & 1) * (16 * NT);
-    const int l15 = lane & 15, l4 = lane >> 4;
-    const double fd = (double)d;
-#pragma unroll
-    for (int jt = 0; jt < NT; ++jt) {
-        const int j = j0 + wc + 16 * jt + l15;
-        if (j >= N) continue;
-        const double nj = stat[TBX + j - j0][0], sj = stat[TBX + j - j0][1], tj = stat[TBX + j - j0][2];
-        const int nops_j = j < n_dom ? 4 : 1;
-#pragma unroll
-        for (int it = 0; it < NT; ++it)
-#pragma unroll
-            for (int e = 0; e < 4; ++e) {
-                const int i = i0 + wr + 16 * it + l4 + 4 * e;
-                if (i >= i_end) continue;
-                const double ni = stat[i - i0][0], si = stat[i - i0][1], ti = stat[i - i0][2];
-                double r2 = fma(-2.0, t.v[it][jt][e], ni + nj);
-                r2 = r2 < 0.0 ? 0.0 : r2;
-                double kda[4][4];                // the pair's entries of K_a; this launch writes its row OX
-                gram_da_pair(a, fd, r2, ti - tj, si - sj, kda);
-                double *orow = out + (int64_t)(i - i_lo) * ld;
-#pragma unroll
-                for (int oy = 0; oy < 4; ++oy) {
-                    if (oy >= nops_j) continue;
-                    const int64_t col = oy == 0 ? j : (int64_t)N + (int64_t)(oy - 1) * n_dom + j;
-                    if (col < ncols) orow[col] = kda[OX][oy];
-                }
-            }
-    }
-}
 
 // v_out[r] = sum_j P[r][j] alpha[j] for the panel's rows r < nrows: one wave per row
 __global__ __launch_bounds__(kLooThreads) void gp_loo_panel_gemv_kernel(const double *__restrict__ P, int64_t ldp, int nrows, int64_t M,
@@ -192,50 +113,6 @@ __global__ __launch_bounds__(kLooThreads) void gp_loo_sum_kernel(const double *_
     q_out[i] = s;
 }
 
-// the rows [row0, row0 + nrows) of K_a, cut at the operator boundaries of the feature order as scasml_gp_gram_rows cuts them; the caller has
-// checked the sizes (every piece has at most 65535 row tiles)
-template <int OX>
-static bool launch_gram_da_rows_of(int32_t d, double a, const float *x_dom, int32_t n_dom, const float *x_bdy, int32_t n_bdy, int i_lo, int n_i,
-                                   int64_t ncols, double *out, int64_t ld, hipStream_t stream) {
-    if (hipFuncSetAttribute(reinterpret_cast<const void *>(gp_gram_da_rows_kernel<OX>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                            (int)tile_lds_bytes<2>()) != hipSuccess)
-        return false;
-    hipLaunchKernelGGL(gp_gram_da_rows_kernel<OX>, dim3((unsigned)((n_dom + n_bdy + 63) / 64), (unsigned)((n_i + 63) / 64)), dim3(kLooThreads),
-                       tile_lds_bytes<2>(), stream, d, a, x_dom, n_dom, x_bdy, n_bdy, i_lo, n_i, ncols, out, ld);
-    return true;
-}
-
-static int launch_gram_da_rows(int32_t d, double a, const float *x_dom, int32_t n_dom, const float *x_bdy, int32_t n_bdy, int64_t row0, int32_t nrows,
-                               int64_t ncols, double *out, int64_t ld, hipStream_t stream) {
-    const int N = n_dom + n_bdy;
-    int64_t r = row0;
-    const int64_t r_end = row0 + nrows;
-    while (r < r_end) {
-        int ox, i_lo;
-        int64_t seg_end;                          // first row past this operator's block
-        if (r < N) {
-            ox = 0;
-            i_lo = (int)r;
-            seg_end = N;
-        } else {
-            const int64_t q = r - N;
-            ox = 1 + (int)(q / n_dom);
-            i_lo = (int)(q % n_dom);
-            seg_end = (int64_t)N + (int64_t)ox * n_dom;
-        }
-        const int64_t stop = seg_end < r_end ? seg_end : r_end;
-        const int n_i = (int)(stop - r);
-        double *seg = out + (r - row0) * ld;
-        const bool ok = ox == 0   ? launch_gram_da_rows_of<0>(d, a, x_dom, n_dom, x_bdy, n_bdy, i_lo, n_i, ncols, seg, ld, stream)
-                        : ox == 1 ? launch_gram_da_rows_of<1>(d, a, x_dom, n_dom, x_bdy, n_bdy, i_lo, n_i, ncols, seg, ld, stream)
-                        : ox == 2 ? launch_gram_da_rows_of<2>(d, a, x_dom, n_dom, x_bdy, n_bdy, i_lo, n_i, ncols, seg, ld, stream)
-                                  : launch_gram_da_rows_of<3>(d, a, x_dom, n_dom, x_bdy, n_bdy, i_lo, n_i, ncols, seg, ld, stream);
-        if (!ok) return fail(SCASML_ERR_HIP, "gp_gram_da_rows: cannot reserve LDS");
-        r = stop;
-    }
-    return 0;
-}
-
 // the panel height in use: the caller's, else the default; never more than M rounded up to the tile
 static int64_t loo_panel_rows(int64_t M, int32_t panel_rows) {
     const int64_t cover = (M + kLooTile - 1) / kLooTile * kLooTile;
@@ -257,7 +134,7 @@ extern "C" int scasml_gp_gram_da_rows(int32_t d, double a, const float *x_dom, i
         return fail(SCASML_ERR_UNSUPPORTED, "gp_gram_da_rows: too many collocation points for one launch");
     if (((int64_t)nrows + 63) / 64 > 65535) return fail(SCASML_ERR_UNSUPPORTED, "gp_gram_da_rows: too many rows per call");
     if (nrows == 0 || ncols == 0) return 0;
-    const int rc = launch_gram_da_rows(d, a, x_dom, n_dom, x_bdy, n_bdy, row0, nrows, ncols, out, ld, (hipStream_t)stream);
+    const int rc = launch_gram_rows<kGramKa>("gp_gram_da_rows", {d, x_dom, n_dom, x_bdy, n_bdy}, a, row0, nrows, ncols, out, ld, (hipStream_t)stream);
     return rc ? rc : check_launch("gp_gram_da_rows launch");
 }
 
@@ -286,7 +163,7 @@ extern "C" int scasml_gp_loo_da(int32_t d, double a, const float *x_dom, int32_t
     double *panel = work, *partials = work + pr * M;
     for (int64_t row0 = 0; row0 < M; row0 += pr) {
         const int nrows = (int)(M - row0 < pr ? M - row0 : pr);
-        const int rc = launch_gram_da_rows(d, a, x_dom, n_dom, x_bdy, n_bdy, row0, nrows, M, panel, M, s);
+        const int rc = launch_gram_rows<kGramKa>("gp_gram_da_rows", {d, x_dom, n_dom, x_bdy, n_bdy}, a, row0, nrows, M, panel, M, s);
         if (rc) return rc;
         hipLaunchKernelGGL(gp_loo_panel_gemv_kernel, dim3((unsigned)((nrows + 3) / 4)), dim3(kLooThreads), 0, s, panel, M, nrows, M, alpha, v_out + row0);
         hipLaunchKernelGGL(gp_loo_tile_kernel, dim3((unsigned)nct, (unsigned)((nrows + kLooTile - 1) / kLooTile)), dim3(kLooThreads), tile_lds_bytes<2>(), s,

@@ -41,6 +41,22 @@ inline bool first_bad_term(const scasml_plan &plan, int &np, int &l) {
     return false;
 }
 
+// The feature rows [row0, row0 + nrows) of a Gram matrix cut at the operator boundaries of the feature order [u(dom), u(bdy), Lap(dom), dt(dom),
+// div(dom)]: fn(ox, i_lo, n_i, row_offset) for every piece in rising row order -- operator ox (0 = I, 1 = Lap, 2 = dt, 3 = div) at the points
+// [i_lo, i_lo + n_i), its first row row_offset rows after row0.  fn returns 0 to go on; any other value ends the walk and is returned.
+template <class Fn>
+inline int for_each_operator_segment(int32_t n_dom, int32_t n_bdy, int64_t row0, int64_t nrows, Fn fn) {
+    const int64_t N = (int64_t)n_dom + n_bdy, r_end = row0 + nrows;
+    for (int64_t r = row0; r < r_end;) {
+        const int ox = r < N ? 0 : 1 + (int)((r - N) / n_dom);
+        const int64_t first = ox == 0 ? 0 : N + (int64_t)(ox - 1) * n_dom, past = ox == 0 ? N : first + n_dom;   // this operator's block of rows
+        const int64_t stop = past < r_end ? past : r_end;
+        if (const int rc = fn(ox, (int)(r - first), (int)(stop - r), r - row0)) return rc;
+        r = stop;
+    }
+    return 0;
+}
+
 // host + device where the HIP compiler sees it (the kernels' tile order), plain host code in plan_host.cpp (scasml_tile_order: the CPU tests)
 #if defined(__HIPCC__)
 #define SCASML_HD __host__ __device__

@@ -151,7 +151,7 @@ def test_loo_kernels_use_no_scratch(tmp_path):
         pytest.skip("no hipcc at %s" % hipcc)
     out = subprocess.run([sys.executable, os.path.join(ROOT, "tools", "kernel_regs.py"), "gp_loo.hip"], capture_output=True, text=True, check=True,
                          env=dict(os.environ, KERNEL_REGS_OUT=str(tmp_path / "gp_loo.s"))).stdout
-    for kernel, count in (("gp_gram_da_rows_kernel", 4), ("gp_loo_panel_gemv_kernel", 1), ("gp_loo_tile_kernel", 1), ("gp_loo_sum_kernel", 1)):
+    for kernel, count in (("gp_gram_rows_kernel", 4), ("gp_loo_panel_gemv_kernel", 1), ("gp_loo_tile_kernel", 1), ("gp_loo_sum_kernel", 1)):
         lines = [l for l in out.splitlines() if kernel in l]
         assert len(lines) == count, out
         for line in lines:

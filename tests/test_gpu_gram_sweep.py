@@ -5,7 +5,7 @@ scasml_gp_gram_compat, scasml_gp_gram_compat_rows and scasml_gp_cross_rows (one 
 switch on, and what the shape lists below are built round (test_the_sweep_covers_every_chunk_tile_and_block_edge checks them):
 
 * NB = 32 (gp_train.hip:17): the MFMA tiles stream the K = d + 1 coordinates through LDS NB at a time, zero-padding the last chunk.
-* TBX = 32 * NT, NT = 2 (gp_gram_mfma_kernel, gp_gram_rows_mfma_kernel): 64 x 64 collocation pairs per workgroup, a 64-point tile edge.
+* TBX = 32 * NT, NT = 2 (gp_gram_mfma_kernel, gp_gram_rows_kernel; kGramTile of csrc/gp_gram_tile.hpp): 64 x 64 collocation pairs per workgroup, a 64-point tile edge.
 * 16 x 16 thread blocks (dim3(16, 16) in scasml_gp_gram_compat / _compat_rows / _cross_rows): a 16-point block edge.
 
 The reference (DirectGP, DirectGPCompat) is oracle/gp.py and oracle/gp_compat.py with the pair geometry taken from exact differences
