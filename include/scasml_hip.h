@@ -627,6 +627,20 @@ int scasml_gp_rff_functionals(int32_t d, double a, const float *x, int64_t n, in
                               double *out, void *stream);
 int scasml_gp_rff_noise(int64_t M, uint64_t seed, int64_t sample0, int64_t S, double *out, int64_t ld, void *stream);
 
+/* Added within ABI 7 (additive).  The gradient of the same prior draws, float64, time derivative last:
+ *   out[(s*n + i)*ld_out + k] = d_k u = F^-1/2 sum_f omega_fk Q_f(x_i),   k = 0 .. d,   ld_out >= d + 1 (columns d + 1 .. ld_out are not touched)
+ * with theta_f, Q_f, omega_f, wc_f, ws_f exactly those of scasml_gp_rff_functionals -- the same Philox addressing, the same omega = sqrt(a) * (double)v --
+ * so that draw s of this entry is the gradient of draw s of that one: its component d is that entry's dt and its first d components sum to div, to
+ * rounding.
+ * One workgroup owns one draw and 64 points and sweeps the features 64 at a time, a product of two products on v_mfma_f64_16x16x4_f64: theta as above
+ * (K = d + 1), sincos in double, Q through LDS once, then G (64 points x 64 components) += Q omega for each of the ceil((d + 1) / 64) <= 4 component
+ * tiles (K = the 64 features), omega regenerated from Philox in the second product's layout; G stays in registers across the feature tiles
+ * (csrc/gp_rff_grad.hip).  Nothing of size S x F x (d+1) or S x n x F reaches HBM; no atomics, no scratch, one fixed summation order.  A point's d + 1
+ * values are a function of (x_i, d, a, F, seed, sample0 + s) alone, bit for bit: not of n, ld_x, ld_out, the point's position, S or the split of draws
+ * over calls.  The refusals of scasml_gp_rff_functionals, in its order, and ld_out < d + 1 (SCASML_ERR_ARG, with ld_x); n = 0 or S = 0 does nothing. */
+int scasml_gp_rff_gradient(int32_t d, double a, const float *x, int64_t n, int64_t ld_x, int32_t F, uint64_t seed, int64_t sample0, int64_t S,
+                           double *out, int64_t ld_out, void *stream);
+
 /* Added within ABI 7 (additive).  The device pieces of the GP log marginal likelihood and its gradient (csrc/gp_evidence.hip), float64:
  *   LML = -1/2 z^T alpha - 1/2 log det K_p - M/2 log(2 pi),   K_p = K(a) + nugget I,  alpha = K_p^-1 z,  a = 1 / sigma^2
  *   dLML/da = 1/2 alpha^T K_a alpha - 1/2 tr(K_p^-1 K_a),     K_a = dK/da

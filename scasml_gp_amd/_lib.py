@@ -133,6 +133,8 @@ SIGNATURES = {
     "scasml_gp_sample": (C.c_int, [C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_uint64, C.c_int64, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p]),
     "scasml_gp_rff_functionals": (C.c_int, [C.c_int32, C.c_double, C.c_void_p, C.c_int64, C.c_int64, C.c_int32, C.c_uint64, C.c_int64, C.c_int64, C.c_void_p,
                                             C.c_void_p]),
+    "scasml_gp_rff_gradient": (C.c_int, [C.c_int32, C.c_double, C.c_void_p, C.c_int64, C.c_int64, C.c_int32, C.c_uint64, C.c_int64, C.c_int64, C.c_void_p,
+                                         C.c_int64, C.c_void_p]),
     "scasml_gp_rff_noise": (C.c_int, [C.c_int64, C.c_uint64, C.c_int64, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p]),
     "scasml_chol_logdet": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]),
     "scasml_gp_gram_da_contract_doubles": (C.c_int64, [C.c_int32, C.c_int32]),

@@ -1,6 +1,6 @@
 // The FP64 matrix-core tile: accumulators, the LDS operand panels and the double-buffered K loop.  Its users: gp_train.hip (Cholesky and
 // triangular-solve updates), gp_gram_tile.hpp (the Gram pair tile of gp_train.hip, gp_evidence.hip and gp_loo.hip), gp_loo.hip (A K_a) and
-// gp_rff.hip (x . omega).  gp_variance.hip keeps a K loop of its own over the same LDS layout: on this one it measured 0.3 % slower.
+// gp_rff.hip and gp_rff_grad.hip (x . omega).  gp_variance.hip keeps a K loop of its own over the same LDS layout: on this one it measured 0.3 % slower.
 //
 // ---- C(TB x TB) += A(TB x K) * B(K x TB) on the FP64 matrix cores ------------------------------------
 // v_mfma_f64_16x16x4_f64: lane l supplies A[row = l&15][k = l>>4] and B[k = l>>4][col = l&15]; the four

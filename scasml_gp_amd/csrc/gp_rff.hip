@@ -14,6 +14,7 @@
 // group of the stage (columns 4 q .. 4 q + 3 of rows r, r + 8, .. r + 56) draw two of its eight Philox blocks each and hand the components round
 // inside the quad of lanes (DPP quad_perm: no LDS, no barrier) -- two Philox blocks per thread and stage, none drawn twice, and no S x F x (d+1)
 // array in HBM.  The K loop runs over d + 3 columns so that wc and ws are met on the way (they enter B as zeros).
+// (The generation of a stage is rff_stage_fetch of gp_rff_stage.hpp, shared with the gradient kernel of gp_rff_grad.hip.)
 // The per-feature statistics (|omega_x|^2, sum omega_x, omega_t, wc, ws) are formed while the stages are generated: a thread draws the same
 // column group (mod 8) of the same two features in every stage, so it sums its share in registers; after the K loop the eight shares of a
 // feature are added in rising order in LDS.
@@ -23,23 +24,11 @@
 // LDS; one multiplication by F^-1/2.  No atomics, no scratch.
 // A point's four values are a function of (x_i, d, a, F, seed, draw index) alone, bit for bit: an MFMA output row depends on its own A row and
 // on B, B and the statistics on (seed, draw, feature tile), and the order of every sum is fixed by the feature index.
-#include "common.hpp"
-#include "f64_mfma_tile.hpp"
-#include "philox_normal.hpp"
+#include "gp_rff_stage.hpp"
 
 namespace scasml {
 
-constexpr int kRffTile = 64, kRffThreads = 256;
 constexpr int kRffStats = 5;                 // -|omega_x|^2, omega_t, sum omega_x, wc, ws
-
-// lane `src` (0..3) of every quad of lanes hands its value to all four; src is a constant once the caller's loop is unrolled
-template <int SRC>
-__device__ __forceinline__ float quad_lane(float v) {
-    return __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), SRC * 0x55, 0xf, 0xf, false));
-}
-__device__ __forceinline__ float quad_broadcast(float v, int src) {
-    return src == 0 ? quad_lane<0>(v) : src == 1 ? quad_lane<1>(v) : src == 2 ? quad_lane<2>(v) : quad_lane<3>(v);
-}
 
 __global__ __launch_bounds__(kRffThreads) void gp_rff_kernel(int d, double sqrt_a, const float *__restrict__ x, int64_t n, int64_t ld_x, int F, double inv_sqrt_f,
                                                             uint32_t k0, uint32_t k1, uint32_t root0, int64_t tiles, double *__restrict__ out) {
@@ -69,51 +58,19 @@ __global__ __launch_bounds__(kRffThreads) void gp_rff_kernel(int d, double sqrt_
         TileAcc<NT> t;
         mfma_tile_zero(t);
         mfma_tile_k_loop<NT>(smem, 0, kend, [&](int64_t kk, double (&ra)[PER], double (&rb)[PER]) {
-#pragma unroll
-            for (int e = 0; e < PER; ++e) {
-                const int idx = tid + e * kRffThreads, rr = idx / NB, cc = idx % NB;
-                const int64_t p = p0 + rr;
-                ra[e] = (p < n && kk + cc < kdim) ? (double)x[p * ld_x + kk + cc] : 0.0;
-            }
-            // blocks e = 2 m4 and 2 m4 + 1 of this quad of lanes: features f0 + rbase + 8 e, columns kk + 4 qs .. + 3
-            float4 blk[2];
-            const int col0 = (int)kk + 4 * qs;
-#pragma unroll
-            for (int h = 0; h < 2; ++h) {
-                const int fr = rbase + 8 * (2 * m4 + h), f = f0 + fr;
-                blk[h] = make_float4(0.f, 0.f, 0.f, 0.f);
-                if (col0 < kend) {                            // features past F: zeros, so that P = Q = 0
-                    const float4 v = f < F ? normal4((uint32_t)(col0 >> 2), (uint32_t)f, root, SCASML_STREAM_GP_RFF, k0, k1) : blk[h];
-                    const float c[4] = {v.x, v.y, v.z, v.w};
-                    float b[4];
-#pragma unroll
-                    for (int j = 0; j < 4; ++j) {
-                        const int k = col0 + j;
-                        const double om = sqrt_a * (double)c[j];
-                        if (k < d) {
-                            w2[h] = fma(om, om, w2[h]);
-                            w1[h] += om;
-                        } else if (k == d) {
-                            stat[fr][1] = om;
-                        } else if (k == d + 1) {
-                            stat[fr][3] = (double)c[j];
-                        } else if (k == d + 2) {
-                            stat[fr][4] = (double)c[j];
-                        }
-                        b[j] = k < kdim ? c[j] : 0.f;
-                    }
-                    blk[h] = make_float4(b[0], b[1], b[2], b[3]);
+            rff_stage_fetch(d, sqrt_a, x, n, ld_x, F, k0, k1, root, p0, f0, kk, ra, rb, [&](int h, int fr, int k, float c, double om) {
+                if (k < d) {
+                    w2[h] = fma(om, om, w2[h]);
+                    w1[h] += om;
+                } else if (k == d) {
+                    stat[fr][1] = om;
+                } else if (k == d + 1) {
+                    stat[fr][3] = (double)c;
+                } else if (k == d + 2) {
+                    stat[fr][4] = (double)c;
                 }
-            }
-            // element e of this thread is component m4 of block e, held by lane e / 2 of the quad as its block e % 2
-#pragma unroll
-            for (int e = 0; e < PER; ++e) {
-                const float4 &b = blk[e % 2];
-                const float c0 = quad_broadcast(b.x, e / 2), c1 = quad_broadcast(b.y, e / 2), c2 = quad_broadcast(b.z, e / 2), c3 = quad_broadcast(b.w, e / 2);
-                rb[e] = sqrt_a * (double)(m4 == 0 ? c0 : m4 == 1 ? c1 : m4 == 2 ? c2 : c3);
-            }
+            });
         }, [] {}, t);
-        static_assert(PER == 8, "the quad hand-over is written for eight elements per thread");
 #pragma unroll
         for (int h = 0; h < 2; ++h) {
             share[rbase + 8 * (2 * m4 + h)][qs][0] = w2[h];
@@ -176,14 +133,6 @@ __global__ __launch_bounds__(kRffThreads) void gp_rff_noise_kernel(int64_t M, ui
 #pragma unroll
     for (int j = 0; j < 4; ++j)
         if (4 * quad + j < M) out[s * ld + 4 * quad + j] = (double)c[j];
-}
-
-static int check_draws(const char *who, int64_t sample0, int64_t S) {
-    if (S < 0 || sample0 < 0) return fail(SCASML_ERR_ARG, "%s: negative draw count or index", who);
-    if (sample0 > (int64_t)1 << 32 || S > ((int64_t)1 << 32) - sample0)
-        return fail(SCASML_ERR_UNSUPPORTED, "%s: draw indices %lld .. %lld reach 2^32 (the Philox root word is 32 bits)", who, (long long)sample0,
-                    (long long)sample0 + (long long)S - 1);
-    return 0;
 }
 
 }  // namespace scasml

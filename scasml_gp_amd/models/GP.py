@@ -13,7 +13,8 @@ What runs where:
 * log marginal likelihood, its gradient in (log sigma, log nugget) and a fit of the two (no counterpart: :25-26 hard-code them; compat=None only)
   .............................................................. scasml_chol_logdet, scasml_gp_gram_da_contract
 * posterior draws as functions (no counterpart; compat=None only): GP.sample_functions -> GPFunctionDraws ... scasml_gp_rff_functionals,
-  scasml_gp_rff_noise, scasml_trsm_lower, scasml_gp_cross_rows, scasml_gemm_nt_sub
+  scasml_gp_rff_noise, scasml_trsm_lower, scasml_gp_cross_rows, scasml_gemm_nt_sub; their gradients (GPFunctionDraws.gradient) and the float64
+  gradient of the mean (GP.posterior_mean_gradient) ... scasml_gp_rff_gradient, scasml_gp_cross_rows (op 0, op 2), scasml_gemm_nt_sub
 
 Two surrogates (``compat``):
 * ``None``: the operators the reference documents -- exact Laplacian features, no float16 rounding.
@@ -175,6 +176,18 @@ class GPFunctionDraws(object):
     def functionals(self, x):
         """(S, n, 4) float64: u, Lap u, dt u and div u (= sum_k d_k u, as everywhere in this library) of every draw at the points x."""
         out, was_numpy = self._evaluate(x, (0, 1, 2, 3))
+        return out.cpu().numpy() if was_numpy else out
+
+    def gradient(self, x):
+        """(S, n, d+1) float64: the gradient of every draw at the points x, time derivative last (NumPy in, NumPy out; CUDA tensor in, CUDA tensor
+        out): the prior term by scasml_gp_rff_gradient, the data term by GP._data_gradient (the gradient of k(x, phi)^T right_vectors[s] without the
+        n x M x (d+1) rows of scasml_gp_cross_rows' op 4).  Component d is functionals(x)[..., 2] and the first d sum to functionals(x)[..., 3], to
+        rounding."""
+        gp = self.gp
+        if gp.compat == "reference":
+            raise ValueError("pathwise draws need compat=None: the as-coded matrix is not the Gram of one kernel and has no spectral density")
+        xi, was_numpy, _ = gp._rows_device(x)
+        out = gp._data_gradient(xi, self._neg, lambda xc: gp._rff_gradient(xc, self.n_features, self.seed, self.sample0, self.n_samples))
         return out.cpu().numpy() if was_numpy else out
 
 
@@ -1206,6 +1219,106 @@ class GP(object):
                                                              int(seed) & 0xFFFFFFFFFFFFFFFF, int(sample0), S, _lib.ptr(out), _lib.stream_ptr()),
                        "gp_rff_functionals")
         return out
+
+    def _rff_gradient(self, xi, n_features, seed, sample0, S):
+        """(S, n, d+1) float64 device tensor: the gradient of the prior draws sample0 .. sample0 + S at the float32 device rows xi."""
+        torch = _lib.require_gpu()
+        out = torch.empty((S, xi.shape[0], self.d + 1), dtype=torch.float64, device="cuda")
+        if out.numel():
+            _lib.check(_lib.load().scasml_gp_rff_gradient(self.d, self.a, _lib.ptr(xi), xi.shape[0], xi.stride(0), int(n_features),
+                                                          int(seed) & 0xFFFFFFFFFFFFFFFF, int(sample0), S, _lib.ptr(out), self.d + 1, _lib.stream_ptr()),
+                       "gp_rff_gradient")
+        return out
+
+    def _data_gradient(self, xi, neg, prior=None):
+        """(S, n, d+1) float64 on the device: the gradient in x of k(x, phi)^T v_s at the float32 device rows xi, time derivative last, for the S
+        vectors v_s = -neg[s, :M] (neg: (S, Mp) float64, the padding zero: what scasml_gemm_nt_sub takes); prior(xc) -> (S, c, d+1), if given, is
+        added chunk by chunk.  compat=None only.
+
+        With c0, cL, ct, cS the u, Lap, dt, div entries of v_s per collocation point y_j (boundary points: c0 only), K0 the op-0 cross rows and
+        r = x_i - y_j (gp_gradient_kernel's identity, in float64 and without the n x M x (d+1) rows of op 4):
+            kE_ij = K0[i,u_j] c0_j + K0[i,Lap_j] cL_j + K0[i,dt_j] ct_j + K0[i,div_j] cS_j        alpha_ij = a (2a K0[i,u_j] cL_j - kE_ij)
+            d_k = x_ik sum_j alpha_ij - sum_j alpha_ij y_jk + a sum_j K0[i,u_j] cS_j   (k < d)      d_t = (op-2 row) . v_s
+        alpha is elementwise torch (_gradient_alpha_pass); every sum over j is a scasml_gemm_nt_sub (alpha against the collocation coordinates and a
+        row of ones, K0 against a cS_j, the op-2 rows against v), whose row i depends on row i of its operands alone -- so a point's values are the
+        same bits however the points are split, permuted or chunked.  x is walked in chunks that keep a (points x Mp) row buffer under
+        variance_buffer_bytes."""
+        torch = _lib.require_gpu()
+        d, a, N, Nb = self.d, self.a, self.N_domain, self.N_boundary
+        S, n, Mp = neg.shape[0], xi.shape[0], neg.shape[1]
+        out = torch.empty((S, n, d + 1), dtype=torch.float64, device="cuda")
+        if S == 0 or n == 0:
+            return out
+        f64 = dict(dtype=torch.float64, device="cuda")
+        Np = _round_up(N + Nb, 32)
+        yext = torch.zeros((d + 1, Np), **f64)                                   # rows 0 .. d: the collocation coordinates; row d: ones
+        yext[:d, :N] = self._xd[:, :d].t()
+        yext[:d, N:N + Nb] = self._xb[:, :d].t()
+        yext[d, :N + Nb] = 1.0
+        neg_div = torch.zeros((S, Mp), **f64)                                    # C -= K0 neg_div^T adds a sum_j K0[i,u_j] cS_j
+        neg_div[:, :N] = a * neg[:, 3 * N + Nb:4 * N + Nb]
+        chunk = int(max(1, min(self.variance_buffer_bytes // (8 * Mp), self.cross_rows_per_call, n)))
+        rows = torch.zeros((chunk, Mp), **f64)                                   # columns M .. Mp stay zero: the cross rows fill 0 .. M
+        x64 = xi[:, :d].to(torch.float64)
+        for lo in range(0, n, chunk):
+            xc = xi[lo:lo + chunk]
+            c = xc.shape[0]
+            tail = torch.zeros((c, 2, S), **f64)                                 # [:, 0, s] = d_t,  [:, 1, s] = a sum_j K0[i,u_j] cS_j
+            self._cross_rows(self._xd, self._xb, 2, xc, rows, Mp, 0)
+            self._gemm_nt_sub(tail[:, 0, :], rows, Mp, neg, Mp)
+            self._cross_rows(self._xd, self._xb, 0, xc, rows, Mp, 0)
+            self._gemm_nt_sub(tail[:, 1, :], rows, Mp, neg_div, Mp)
+            self._gradient_alpha_pass(rows[:c], x64[lo:lo + c], neg, yext, tail, out[:, lo:lo + c])
+            if prior is not None:
+                out[:, lo:lo + c] += prior(xc)
+        return out
+
+    @staticmethod
+    def _gemm_nt_sub(Cm, A, lda, B, K):
+        """Cm (its own shape and row stride) -= A (lda) B^T over K columns: the one call of scasml_gemm_nt_sub of the gradient routines."""
+        _lib.check(_lib.load().scasml_gemm_nt_sub(_lib.ptr(Cm), Cm.stride(0), Cm.shape[0], Cm.shape[1], _lib.ptr(A), lda, _lib.ptr(B), B.stride(0), K,
+                                                  0, 0, 0, _lib.stream_ptr()), "gemm_nt_sub")
+
+    def _gradient_alpha_pass(self, K0, x64, neg, yext, tail, out):
+        """out (S, c, d+1) <- the data-term gradient of one chunk from its op-0 rows K0 (c, Mp), its spatial coordinates x64 (c, d) and tail (c, 2, S)
+        (_data_gradient).  The draws go in groups that keep alpha and its two temporaries, (group x c x N) doubles each, under variance_buffer_bytes:
+        alpha is elementwise torch over the whole group, and ONE scasml_gemm_nt_sub of its (group c) rows against [Y, 1] sums over j."""
+        torch = _lib.require_gpu()
+        d, a, N, Nb = self.d, self.a, self.N_domain, self.N_boundary
+        S, c, Np = neg.shape[0], K0.shape[0], yext.shape[1]
+        ku, kb = K0[None, :, :N], K0[None, :, N:N + Nb]
+        kL, kt, kS = (K0[None, :, k * N + Nb:(k + 1) * N + Nb] for k in (1, 2, 3))
+        group = int(max(1, min(S, self.variance_buffer_bytes // (24 * Np * c))))
+        for j0 in range(0, S, group):
+            v = -neg[j0:j0 + group, None, :]                                     # (g, 1, Mp): the group's vectors
+            g = v.shape[0]
+            c0, c0b = v[:, :, :N], v[:, :, N:N + Nb]
+            cL, ct, cS = (v[:, :, k * N + Nb:(k + 1) * N + Nb] for k in (1, 2, 3))
+            alpha = torch.zeros((g, c, Np), dtype=torch.float64, device="cuda")  # columns N + Nb .. Np stay zero
+            kE = ku * c0
+            kE.addcmul_(kL, cL).addcmul_(kt, ct).addcmul_(kS, cS)
+            alpha[:, :, :N] = (ku * (2.0 * a * cL)).sub_(kE).mul_(a)
+            alpha[:, :, N:N + Nb] = kb * (-a * c0b)
+            acc = torch.zeros((g, c, d + 1), dtype=torch.float64, device="cuda")  # <- -alpha [Y, 1]: columns k < d, then -sum_j alpha_ij
+            self._gemm_nt_sub(acc.view(g * c, d + 1), alpha, Np, yext, Np)
+            t = tail[:, :, j0:j0 + g].permute(2, 0, 1)                           # (g, c, 2)
+            out[j0:j0 + g, :, :d] = acc[:, :, :d] - x64[None] * acc[:, :, d:] + t[:, :, 1:]
+            out[j0:j0 + g, :, d] = t[:, :, 0]
+
+    def posterior_mean_gradient(self, x_t_infer):
+        '''(n, d+1) float64 gradient of the posterior mean k(x, phi)^T right_vector, time derivative last (NumPy in, NumPy out; CUDA tensor in,
+        CUDA tensor out): the float64 statement of compute_gradient, which is the float32 kernel the solvers use and does not change.  The data
+        term of GPFunctionDraws.gradient applied to right_vector (_data_gradient); every point's values are a function of that point alone, bit for
+        bit.  compat=None only.'''
+        torch = _lib.require_gpu()
+        if self.compat == "reference":
+            raise ValueError("posterior_mean_gradient needs compat=None: the as-coded matrix is not the Gram of one kernel and has no spectral density")
+        self._require_trained()
+        xi, was_numpy, _ = self._rows_device(x_t_infer)
+        neg = torch.zeros((1, _round_up(self.phi_dim, 32)), dtype=torch.float64, device="cuda")
+        neg[0, :self.phi_dim] = -torch.from_numpy(np.ascontiguousarray(self.right_vector, dtype=np.float64).reshape(-1)).cuda()
+        out = self._data_gradient(xi, neg)[0]
+        return out.cpu().numpy() if was_numpy else out
 
     def sample_functions(self, n_samples, seed=0, n_features=2048, sample0=0, z=None):
         '''n_samples posterior draws as functions (GPFunctionDraws: .right_vectors, .predict(x), .functionals(x)), by pathwise conditioning
