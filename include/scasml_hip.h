@@ -593,6 +593,22 @@ int scasml_gp_cross_rows(int32_t d, double a, const float *x_dom, int32_t n_dom,
  * depend on n, on the row's position or on the other rows.  n = 0 does nothing. */
 int scasml_gp_variance(const double *L, int64_t Mp, double *rows, int64_t ld, int64_t n, double prior, double *var_out, void *stream);
 
+/* Added within ABI 7 (additive; models/GP.py keeps only right_vector and has no counterpart).  Posterior covariance of the four functionals
+ * [u, Lap u, dt u, div u] of the surrogate at n_points points, float64:
+ *   cov_out[16 i + 4 o + p] = prior_h[4 o + p] - (L^-1 k_o(x_i)) . (L^-1 k_p(x_i)),   o, p = 0 u, 1 Lap, 2 dt, 3 div (scasml_gp_cross_rows' numbering)
+ * from the factor L of scasml_gp_variance (Mp x Mp row-major, Mp a multiple of 32) and the op-0 .. op-3 feature rows of scasml_gp_cross_rows,
+ * interleaved: `rows` is (4 n_points) x ld row-major, row 4 i + o the op-o row of point i in rows[(4 i + o)*ld .. + Mp) with columns M .. Mp zero.
+ * `rows` is OVERWRITTEN with rows L^-T.  prior_h: 16 HOST doubles, row-major 4 x 4, the prior covariance of the four functionals at one point -- for
+ * kappa = exp(-a |x - y|^2 / 2) in d space dimensions [1, -a d, 0, 0; -a d, (d^2 + 2 d) a^2, 0, 0; 0, 0, a, 0; 0, 0, 0, a d]; they travel as kernel
+ * arguments.  One launch of the variance tile with four rows per point (csrc/gp_functional_cov.hip, gp_variance_tile.hpp): a workgroup owns 16
+ * points, the four rows of a point sit in one lane quad of the substitution, and every solved column adds x_o x_p to the quad's sums in rising column
+ * order (a DPP quad exchange).  No atomics, no scratch; a point's 16 values are a function of its four rows, L and Mp alone, bit for bit; the block is
+ * exactly symmetric; entry (o, o) and the solved rows are the bits scasml_gp_variance(L, Mp, rows, ld, 4 n_points, prior_h[5 o], ...) gives.
+ * The refusals of scasml_gp_variance, in its order: null pointers, Mp < 1, ld < Mp, n_points < 0: SCASML_ERR_ARG; Mp % 32 != 0 or more than 2^31 - 1
+ * tiles: SCASML_ERR_UNSUPPORTED; n_points = 0 does nothing. */
+int scasml_gp_functional_covariance(const double *L, int64_t Mp, double *rows, int64_t ld, int64_t n_points, const double *prior_h, double *cov_out,
+                                    void *stream);
+
 /* Added within ABI 7 (additive).  S draws from N(mean, Lc Lc^T) at n points, float64:
  *   out[s*ld_out + i] = mean[i] + sum_{j <= i} Lc[i*np + j] * z(seed, sample0 + s, j),   i < n, s < S
  * Lc: the lower Cholesky factor of the n x n joint covariance in an np x np row-major buffer, np a multiple of 32, identity-padded as scasml_cholesky

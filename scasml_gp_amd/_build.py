@@ -8,7 +8,7 @@ ROOT = os.path.dirname(HERE)
 CSRC = os.path.join(HERE, "csrc")
 LIBDIR = os.path.join(HERE, "lib")
 LIB = os.path.join(LIBDIR, "libscasml_hip.so")
-SOURCES = ["plan_host.cpp", "picard_tree_jax_deep.hip", "picard_tree.hip", "picard_tree_jax.hip", "picard_tree_stderr_deep.hip", "picard_tree_stderr_uz_deep.hip", "picard_tree_stderr.hip", "picard_tree_stderr_uz.hip", "picard_tree_summands_uz_deep.hip", "picard_tree_summands_deep.hip", "picard_tree_summands_uz.hip", "picard_tree_summands.hip", "picard_staged.hip", "gp_eval.hip", "gp_eval_bf16.hip", "gp_train.hip", "gp_compat.hip", "gp_eval_compat_mfma.hip", "dist_linalg.hip", "gp_variance.hip", "gp_sample.hip", "gp_evidence.hip", "gp_loo.hip", "gp_rff.hip", "gp_rff_grad.hip"]
+SOURCES = ["plan_host.cpp", "picard_tree_jax_deep.hip", "picard_tree.hip", "picard_tree_jax.hip", "picard_tree_stderr_deep.hip", "picard_tree_stderr_uz_deep.hip", "picard_tree_stderr.hip", "picard_tree_stderr_uz.hip", "picard_tree_summands_uz_deep.hip", "picard_tree_summands_deep.hip", "picard_tree_summands_uz.hip", "picard_tree_summands.hip", "picard_staged.hip", "gp_eval.hip", "gp_eval_bf16.hip", "gp_train.hip", "gp_compat.hip", "gp_eval_compat_mfma.hip", "dist_linalg.hip", "gp_variance.hip", "gp_sample.hip", "gp_evidence.hip", "gp_loo.hip", "gp_rff.hip", "gp_rff_grad.hip", "gp_functional_cov.hip"]
 # -ffp-contract=off: the RNG transform is specified in separately rounded IEEE mul/add
 # (philox_normal.hpp); every fused multiply-add elsewhere is written as fmaf() explicitly.
 # -fno-slp-vectorize: hipcc otherwise packs the scalar f32 epilogue into v_pk_fma_f32 / v_pk_mul_f32 plus

@@ -15,6 +15,8 @@ What runs where:
 * posterior draws as functions (no counterpart; compat=None only): GP.sample_functions -> GPFunctionDraws ... scasml_gp_rff_functionals,
   scasml_gp_rff_noise, scasml_trsm_lower, scasml_gp_cross_rows, scasml_gemm_nt_sub; their gradients (GPFunctionDraws.gradient) and the float64
   gradient of the mean (GP.posterior_mean_gradient) ... scasml_gp_rff_gradient, scasml_gp_cross_rows (op 0, op 2), scasml_gemm_nt_sub
+* posterior covariance of [u, Lap u, dt u, div u] at a point and the delta-method variance of the PDE residual (no counterpart; compat=None only):
+  GP.predict_functional_covariance, GP.predict_residual_variance ... scasml_gp_cross_rows (op 0 .. 3), scasml_gp_functional_covariance, scasml_gemm_nt_sub
 
 Two surrogates (``compat``):
 * ``None``: the operators the reference documents -- exact Laplacian features, no float16 rounding.
@@ -747,6 +749,103 @@ class GP(object):
     def predict_std(self, x_t_infer):
         '''(n, 1) float64 posterior standard deviation sqrt(max(predict_variance, 0)).'''
         var = self.predict_variance(x_t_infer)
+        return np.sqrt(np.maximum(var, 0.0)) if isinstance(var, np.ndarray) else var.clamp_min(0.0).sqrt()
+
+    # posterior covariance of the four functionals at a point and the delta-method variance of the PDE residual (no counterpart in models/GP.py)
+    def _functional_prior(self):
+        """(4, 4) float64: the prior covariance of [u, Lap u, dt u, div u] at one point -- the Gram table (csrc/gp_gram_table.hpp) at r = 0."""
+        a, d = self.a, float(self.d)
+        P = np.zeros((4, 4), dtype=np.float64)
+        P[0, 0] = 1.0
+        P[0, 1] = P[1, 0] = -a * d
+        P[1, 1] = (d * d + 2.0 * d) * a * a
+        P[2, 2] = a
+        P[3, 3] = a * d
+        return P
+
+    def _functional_covariance(self, xi, neg=None):
+        """((n, 4, 4) covariance, (n, 4) means or None) on the device for the float32 device rows xi.  The four operators' feature rows go into one
+        zeroed (chunk, 4, Mp) buffer -- operator o at column offset o Mp of a row of 4 Mp doubles, so the rows lie interleaved without a copy -- and
+        scasml_gp_functional_covariance solves them in place.  neg, (1, Mp) = -right_vector padded with zeros: the posterior-mean functionals
+        K_o(x, phi) . right_vector are taken from the same buffer before it is solved (scasml_gemm_nt_sub, one column)."""
+        torch = _lib.require_gpu()
+        lib = _lib.load()
+        L = self._variance_factor()
+        n, Mp = xi.shape[0], L.shape[0]
+        f64 = dict(dtype=torch.float64, device="cuda")
+        cov = torch.empty((n, 4, 4), **f64)
+        mean = torch.zeros((n, 4), **f64) if neg is not None else None
+        if n == 0:
+            return cov, mean
+        prior = np.ascontiguousarray(self._functional_prior())
+        chunk = int(max(1, min(self.variance_buffer_bytes // (32 * Mp), self.cross_rows_per_call, n)))
+        buf = torch.zeros((chunk, 4, Mp), **f64)             # columns M .. Mp stay zero through every solve: L is the identity there
+        for lo in range(0, n, chunk):
+            xc = xi[lo:lo + chunk]
+            c = xc.shape[0]
+            for o in range(4):
+                self._cross_rows(self._xd, self._xb, o, xc, buf[:, o, :], 4 * Mp, 0)
+            if neg is not None:
+                self._gemm_nt_sub(mean[lo:lo + c].view(4 * c, 1), buf, Mp, neg, Mp)
+            _lib.check(lib.scasml_gp_functional_covariance(_lib.ptr(L), Mp, _lib.ptr(buf), Mp, c, prior.ctypes.data_as(C.c_void_p), _lib.ptr(cov[lo:]),
+                                                           _lib.stream_ptr()), "gp_functional_covariance")
+        return cov, mean
+
+    def predict_functional_covariance(self, x_t_infer):
+        '''(n, 4, 4) float64 posterior covariance of [u, Lap u, dt u, div u] at each point (NumPy in, NumPy out; CUDA tensor in, CUDA tensor out; the
+        raw values, not clamped):
+            cov(x)[o][p] = P[o][p] - (L^-1 K_o(x, phi)) . (L^-1 K_p(x, phi))
+        with P the prior covariance of the four functionals at one point (1, -a d, (d^2 + 2 d) a^2, a, a d: the Gram table at r = 0), K_o the op-o
+        feature rows of scasml_gp_cross_rows and L the factor predict_variance uses.  One launch of scasml_gp_functional_covariance per chunk
+        (csrc/gp_functional_cov.hip): n is walked in chunks that keep the (points x 4 x Mp) row buffer under ``variance_buffer_bytes``.  Every point's
+        block is a function of that point alone, bit for bit; it is exactly symmetric, and [:, 0, 0] is predict_variance bit for bit.  It depends on
+        the collocation points, sigma and nugget only -- not on the fit.  compat=None only.'''
+        if self.compat == "reference":
+            raise ValueError("the functional covariance needs compat=None: the as-coded matrix is not the Gram of one kernel and has no derivative in a")
+        xi, was_numpy, _ = self._rows_device(x_t_infer)
+        cov = self._functional_covariance(xi)[0]
+        return cov.cpu().numpy() if was_numpy else cov
+
+    def predict_residual_variance(self, x_t_infer, return_parts=False):
+        '''(n, 1) float64 delta-method variance  c^T cov c  of the PDE residual  r = dt u - F(u, Lap u, div u)  at each point (NumPy in, NumPy out; CUDA
+        tensor in, CUDA tensor out; the raw value, not clamped), cov = predict_functional_covariance(x) and
+            c = [-dF/dz1, -dF/dz3, 1, -dF/dz5]   (equation.F_parts)
+        evaluated at the float64 posterior-mean functionals m_o(x) = K_o(x, phi) . right_vector, which are taken from the covariance's own row buffer
+        before it is solved.  F_parts is host NumPy; the 4 x 4 combine is elementwise, one fixed order: a point's value is a function of that point
+        alone, bit for bit.  return_parts=True: (variance, {"mean": (n, 4) m, "c": (n, 4), "residual": (n, 1) m_dt - F(m)}).  Needs a trained GP and
+        an equation with F_parts (NotImplementedError otherwise); compat=None only.'''
+        torch = _lib.require_gpu()
+        if self.compat == "reference":
+            raise ValueError("the residual variance needs compat=None: the as-coded matrix is not the Gram of one kernel and has no derivative in a")
+        if self.right_vector is None:
+            raise NotImplementedError("the residual variance is linearised at the posterior mean: call GPsolver(x_domain, x_boundary) first")
+        if not callable(getattr(self.equation, "F_parts", None)):
+            raise NotImplementedError("the residual variance needs the equation's collocation operator and its derivatives: %s has no F_parts"
+                                      % type(self.equation).__name__)
+        xi, was_numpy, _ = self._rows_device(x_t_infer)
+        n = xi.shape[0]
+        neg = torch.zeros((1, _round_up(self.phi_dim, 32)), dtype=torch.float64, device="cuda")
+        neg[0, :self.phi_dim] = -torch.from_numpy(np.ascontiguousarray(self.right_vector, dtype=np.float64).reshape(-1)).cuda()
+        cov, mean = self._functional_covariance(xi, neg)
+        m = mean.cpu().numpy()
+        F, (d1, d3, d5) = self.equation.F_parts(m[:, 0], m[:, 1], m[:, 3])[:2]
+        c_h = np.stack([-np.broadcast_to(d1, (n,)), -np.broadcast_to(d3, (n,)), np.ones(n), -np.broadcast_to(d5, (n,))], axis=1).astype(np.float64)
+        c = torch.from_numpy(np.ascontiguousarray(c_h)).cuda()
+        var = torch.zeros((n, 1), dtype=torch.float64, device="cuda")
+        for o in range(4):                                   # sum_o c_o (sum_p cov[o][p] c_p), p then o rising
+            inner = torch.zeros(n, dtype=torch.float64, device="cuda")
+            for p in range(4):
+                inner.addcmul_(cov[:, o, p], c[:, p])
+            var[:, 0].addcmul_(c[:, o], inner)
+        if not return_parts:
+            return var.cpu().numpy() if was_numpy else var
+        res_h = (m[:, 2] - np.asarray(F, dtype=np.float64))[:, None]
+        parts = {"mean": m, "c": c_h, "residual": res_h} if was_numpy else {"mean": mean, "c": c, "residual": torch.from_numpy(res_h).cuda()}
+        return (var.cpu().numpy() if was_numpy else var), parts
+
+    def predict_residual_std(self, x_t_infer):
+        '''(n, 1) float64 sqrt(max(predict_residual_variance, 0)).'''
+        var = self.predict_residual_variance(x_t_infer)
         return np.sqrt(np.maximum(var, 0.0)) if isinstance(var, np.ndarray) else var.clamp_min(0.0).sqrt()
 
     # log marginal likelihood, its gradient and a fit of (sigma, nugget) to it (no counterpart in models/GP.py, which hard-codes both, :25-26)
